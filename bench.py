@@ -14,8 +14,16 @@ solves its own batch of 4096, seed = rank; value summed over the ranks) and repo
 
 Launch: python bench.py [--gpus N --steps K --warmup W]; N>1 via torch.distributed.run.
 Prints ONE JSON line on rank 0.
+
+A plain run does what the headline figure needs and no more: set-up, clock settle, W warm-up
+solves, K timed solves, the result line.  --full adds every other leg (kernel time and roofline,
+the other scaling mode, training, dopri5, ECG, MNIST, ETT, CPU baselines, parity); the --no-* and
+per-leg options act there.  --dump-outputs DIR writes the last timed solve's solution as
+DIR/sol.npy (N > 1: DIR/sol_rank<r>.npy, each rank's own block); weights, y0 and the hysteresis
+state the warm-up starts from are the same bits in every run with the same arguments.
 """
 import argparse
+import contextlib
 import glob
 import json
 import os
@@ -75,6 +83,12 @@ def parse():
     ap.add_argument("--scaling", choices=("strong", "weak"), default="strong",
                     help="strong: global batch 4096 split over the ranks (the contract line); "
                          "weak: 4096 trajectories per rank")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed solves, write the last one's solution (T, B, 2) float32 as DIR/sol.npy "
+                         "(N > 1: each rank its block, DIR/sol_rank<r>.npy)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary leg (kernel time / roofline, the other scaling mode, training, "
+                         "dopri5, ECG, MNIST, ETT, CPU baselines, parity); the options below act only with --full")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-dopri5", action="store_true", help="skip the LV dopri5 (torchdiffeq defaults) line")
     ap.add_argument("--no-ecg", action="store_true", help="skip the ECG dopri5 (configs[2]) line")
@@ -88,12 +102,34 @@ def parse():
     return ap.parse_args()
 
 
+@contextlib.contextmanager
+def reproducible_init():
+    """efficient_kan's init fits the spline weights with torch.linalg.lstsq, whose fp32 LAPACK result
+    moves by an ulp from process to process, and the KAN-FET field amplifies that.
+    Inside this context the same minimum-norm fit (fewer knots than coefficients: pinv(A) B) is done
+    in fp64 and rounded to fp32 once, so the seed alone fixes the weights' bits and two runs, or two
+    builds, solve the same problem."""
+    import types
+    orig = torch.linalg.lstsq
+
+    def lstsq(A, B):
+        sol = torch.linalg.pinv(A.to(torch.float64)) @ B.to(torch.float64)
+        return types.SimpleNamespace(solution=sol.to(A.dtype))
+
+    torch.linalg.lstsq = lstsq
+    try:
+        yield
+    finally:
+        torch.linalg.lstsq = orig
+
+
 def make_problem(rank, world, scaling, dev):
     """Seed-0 weights on every rank; y0: strong = this rank's block of the seed-0 global batch,
     weak = a full batch of its own (seed = rank)."""
     import fet_ode_amd.dist as D
     torch.manual_seed(0)
-    model = F.KANFET([2, 10, 2], grid_size=5)
+    with reproducible_init():
+        model = F.KANFET([2, 10, 2], grid_size=5)
     if world > 1:   # one model for the job: the efficient_kan init is not reproducible across processes
         D.broadcast_parameters(model)
     sd = {k: v.clone() for k, v in model.state_dict().items()}
@@ -1102,6 +1138,12 @@ def main():
             settle_n += 10
             torch.cuda.synchronize(dev)
         settle_s = time.perf_counter() - ts
+        # the settle loop runs for a wall time, so its solve count differs from run to run, and the
+        # hysteresis state carries from solve to solve without reaching a fixed point (a fifth of the
+        # trajectories alternate between two solutions, a few keep moving): the warm-up starts from the
+        # seed-0 model's own hysteresis state again (parameters untouched), so the last timed solve is
+        # solve W + K of that sequence in every run
+        model.load_state_dict({k: v for k, v in sd.items() if k.endswith(("prev_x", "branch_sign"))}, strict=False)
         for _ in range(args.warmup):
             solve()
         torch.cuda.synchronize(dev)
@@ -1119,11 +1161,17 @@ def main():
             tt = torch.tensor([el], device=dev if backend == "nccl" else "cpu", dtype=torch.float64)
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             el = tt.item()
-        k_ms = kernel_time_ms(model, y0d, t)
-    progress("train")
-    train = train_rate(model, y0d, t, args.train_iters, 5, world, strong) if args.train_iters > 0 else None
+        if args.dump_outputs:
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            np.save(os.path.join(args.dump_outputs, "sol.npy" if world == 1 else f"sol_rank{rank}.npy"),
+                    sol.to(torch.float32).cpu().numpy())
+        k_ms = kernel_time_ms(model, y0d, t) if args.full else None
+    train = None
+    if args.full and args.train_iters > 0:
+        progress("train")
+        train = train_rate(model, y0d, t, args.train_iters, 5, world, strong)
     other_line = None
-    if world > 1:
+    if world > 1 and args.full:
         # the other scaling mode from the same run: strong = the global seed-0 batch of 4096 split
         # over the ranks; weak = a batch of 4096 per rank (seed = rank)
         import fet_ode_amd.dist as D
@@ -1152,18 +1200,13 @@ def main():
                           "batch_per_gpu": hi - lo, "unit": "RK4 steps/s of ONE batch-4096 job split over the GPUs",
                           "scaling": "strong"}
     dp5_sharded = None
-    if world > 1 and not args.no_dopri5:
+    if world > 1 and args.full and not args.no_dopri5:
         dp5_sharded = lv_dopri5_sharded_rate(sd, y0d, t, world, B if strong else B * world)
     ms_per_step = el / args.steps * 1e3
     # strong: every solve covers the global batch once; weak: each rank's solve is a batch of its own
     value = (1 if strong else world) * args.steps * STEPS_PER_SOLVE / el
 
     if rank == 0:
-        bytes_launch = alg_bytes_per_step(Bl) * STEPS_PER_SOLVE
-        achieved = bytes_launch / (k_ms * 1e-3) / 1e9
-        traffic, traffic_src = pmc_traffic_per_launch() if Bl == B else (None, None)
-        flops_launch = ALG_FLOPS_PER_TRAJ_STEP * Bl * STEPS_PER_SOLVE
-        tflops = flops_launch / (k_ms * 1e-3) / 1e12
         out = {
             "metric": METRIC, "value": value,
             "unit": "RK4 steps/s of the batch-4096 job" + (" (global batch split over GPUs)" if strong
@@ -1181,6 +1224,16 @@ def main():
                        "batch_per_gpu": Bl, "global_batch": B if strong else B * world,
                        "rk4_steps_per_solve": STEPS_PER_SOLVE,
                        "parallelism": f"trajectory-sharded x{world} (no collective)"},
+        }
+        if not args.full:
+            print(json.dumps(out), flush=True)
+    if rank == 0 and args.full:
+        bytes_launch = alg_bytes_per_step(Bl) * STEPS_PER_SOLVE
+        achieved = bytes_launch / (k_ms * 1e-3) / 1e9
+        traffic, traffic_src = pmc_traffic_per_launch() if Bl == B else (None, None)
+        flops_launch = ALG_FLOPS_PER_TRAJ_STEP * Bl * STEPS_PER_SOLVE
+        tflops = flops_launch / (k_ms * 1e-3) / 1e12
+        out.update({
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
                          "kernel": ("fused4_kernel<10,10,10,12,true,true,false,false,2> (v7 rk4, two trajectories per wave)"
@@ -1204,7 +1257,7 @@ def main():
             # itself has no GEMM-shaped work): the ETT wide KAN-FET layer and the MNIST
             # KANLinear head, from the committed PMC pass (tools/pmc_issue.py)
             "mfma": {k: pmc_mfma(k) for k in ("wide_layer_kernel<10, true, true, 8>", "wide_fwd4_kernel")},
-        }
+        })
         if world == 1:
             # strong-scaling proxy on one GPU: the per-GPU block of an 8-GPU strong-scaled job
             y512 = y0d[:B // 8].contiguous()

@@ -12,11 +12,11 @@ tail -25 $O/pytest_gpu.log
 [ -n "$NO_BENCH" ] && exit 0
 step smoke timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()"
 tail -1 $O/smoke.log
-step bench timeout -k 10 600 python bench.py
+step bench timeout -k 10 600 python bench.py --full
 tail -1 $O/bench.log > $O/bench_$R.json
 cat $O/bench_$R.json
 [ -n "$NO_PROF" ] && exit 0
-step prof_stats timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/prof_$R -o run --output-format csv -- python3 bench.py --steps 200 --warmup 100 --no-cpu-baseline --train-iters 20
+step prof_stats timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/prof_$R -o run --output-format csv -- python3 bench.py --full --steps 200 --warmup 100 --no-cpu-baseline --train-iters 20
 # keep gpurun_out small (it is merged back only below 64 MiB): the stats CSV, not the traces
 f=$(find $O/prof_$R -name '*kernel_stats.csv' | head -1); [ -n "$f" ] && cp "$f" $O/${R}_kernel_stats.csv
 rm -rf $O/prof_$R
