@@ -2035,7 +2035,8 @@ int64_t g_v8_hi = [] {
 }();
 int g_v8_tpb = [] {   // trajectories per v8 workgroup (1: two waves, 2: four waves); env FETODE_V8_TPB
   const char* e = getenv("FETODE_V8_TPB");
-  return e ? atoi(e) : 2;
+  const int v = e ? atoi(e) : 2;
+  return v == 1 || v == 2 ? v : 2;   // anything else is ignored: the default stays
 }();
 uint32_t g_dp_spin_limit = 0;   // fetode_dopri5_set_spin_limit (0: the built-in limits)
 
@@ -2556,6 +2557,12 @@ int64_t fetode_fused_set_v8_range(int64_t lo, int64_t hi) {
   const int64_t prev = g_v8_hi;
   if (lo >= 0) g_v8_lo = lo;
   if (hi >= 0) g_v8_hi = hi;
+  return prev;
+}
+
+int fetode_fused_set_v8_tpb(int tpb) {
+  const int prev = g_v8_tpb;
+  if (tpb == 1 || tpb == 2) g_v8_tpb = tpb;
   return prev;
 }
 

@@ -134,6 +134,11 @@ int64_t fetode_fused_set_tpw1_range(int64_t lo, int64_t hi);
  * every other choice above.  Default (256, 512] (env FETODE_V8_LO / FETODE_V8_HI).  Sets lo / hi
  * when >= 0; returns the previous hi. */
 int64_t fetode_fused_set_v8_range(int64_t lo, int64_t hi);
+/* Trajectories per v8 workgroup: 2 (default: four waves, 256 threads) or 1 (two waves, 128
+ * threads); env FETODE_V8_TPB, where any value but 1 or 2 is ignored.  Sets the value when tpb is
+ * 1 or 2, any other argument changes nothing (so a negative one is a query); returns the previous
+ * value.  Process-wide tuning knob. */
+int fetode_fused_set_v8_tpb(int tpb);
 /* The current switch points, out[5] = {small_batch_max, tpw1_lo, tpw1_hi, v8_lo, v8_hi} (so a
  * caller can save and restore every knob above). */
 int fetode_fused_get_batch_ranges(int64_t* out);

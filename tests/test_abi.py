@@ -4,6 +4,7 @@ import ctypes
 import os
 import re
 import subprocess
+import sys
 
 import pytest
 
@@ -72,6 +73,33 @@ def test_host_queries_without_gpu():
     assert lib.fetode_fused_supported(h.ref) == 1
     assert lib.fetode_fused_supported(_lv_field(F, False).ref) == 1
     assert lib.fetode_state_width(_lv_field(F, False).ref) == 0
+
+
+def test_v8_workgroup_shape_switch(lib):
+    """fetode_fused_set_v8_tpb: 1 or 2 sets, anything else only queries; returns the previous value."""
+    f = lib.fetode_fused_set_v8_tpb
+    f.restype, f.argtypes = ctypes.c_int, [ctypes.c_int]
+    prev = f(-1)
+    try:
+        assert prev in (1, 2) and f(-1) == prev
+        assert f(1) == prev and f(-1) == 1
+        for bad in (0, 3, -7, 1 << 20):
+            assert f(bad) == 1
+        assert f(2) == 1 and f(-1) == 2
+        assert f(0) == 2 and f(-1) == 2
+    finally:
+        f(prev)
+
+
+@pytest.mark.parametrize("env,expect", [(None, 2), ("1", 1), ("2", 2), ("0", 2), ("4", 2), ("x", 2), ("", 2)])
+def test_v8_workgroup_shape_env(lib, env, expect):
+    """FETODE_V8_TPB is read once at load: 1 or 2 is taken, anything else leaves the default of 2."""
+    e = {k: v for k, v in os.environ.items() if k != "FETODE_V8_TPB"}
+    if env is not None:
+        e["FETODE_V8_TPB"] = env
+    code = f"import ctypes; print(ctypes.CDLL({LIB!r}).fetode_fused_set_v8_tpb(-1))"
+    out = subprocess.run([sys.executable, "-c", code], env=e, capture_output=True, text=True, check=True).stdout
+    assert int(out) == expect
 
 
 def test_shape_errors_are_reported():
