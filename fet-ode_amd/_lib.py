@@ -223,6 +223,20 @@ SIGNATURES = {
                                          ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_float), _vp, _vp,
                                          _vp, _vp, _vp, _vp, ctypes.c_int32, _vp]),
     "fetode_ecg_dopri5_workspace": (ctypes.c_int64, [ctypes.c_int64]),
+    "fetode_ecg_dopri5_tape": (ctypes.c_int, [ctypes.POINTER(HLogisticDesc), _vp, _vp, ctypes.c_int32, _vp, _vp,
+                                              ctypes.c_int64, _vp, ctypes.c_int32, ctypes.c_double, ctypes.c_double,
+                                              ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_float), _vp,
+                                              _vp, _vp, _vp, _vp, _vp, ctypes.c_int32, _vp, ctypes.c_int32, _vp,
+                                              _vp]),
+    "fetode_ecg_dopri5_backward_max_batch": (ctypes.c_int64, [ctypes.POINTER(HLogisticDesc)]),
+    "fetode_ecg_dopri5_backward_workspace": (ctypes.c_int64, [ctypes.POINTER(HLogisticDesc), ctypes.c_int64,
+                                                              ctypes.c_int32]),
+    "fetode_ecg_dopri5_backward": (ctypes.c_int, [ctypes.POINTER(HLogisticDesc), _vp, ctypes.c_int32, _vp,
+                                                  ctypes.c_int64, _vp, ctypes.c_int32, ctypes.c_double,
+                                                  ctypes.c_double, ctypes.POINTER(ctypes.c_double),
+                                                  ctypes.POINTER(ctypes.c_float), _vp, _vp, ctypes.c_int32, _vp,
+                                                  ctypes.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                  _vp]),
     "fetode_tanh_bound": (ctypes.c_int, [ctypes.c_int64, ctypes.c_float, _vp, _vp, _vp, _vp]),
     "fetode_tanh_bound_backward": (ctypes.c_int, [ctypes.c_int64, ctypes.c_float, _vp, _vp, _vp, _vp]),
     "fetode_tanh": (ctypes.c_int, [ctypes.c_int64, _vp, _vp, _vp]),

@@ -17,6 +17,7 @@
 #include <cstring>
 
 #include "fetode_common.h"
+#include "fetode_ecg_dev.h"
 
 using namespace fetode;
 
@@ -24,40 +25,6 @@ namespace {
 
 constexpr int kRows = 4;      // batch rows per forward workgroup
 constexpr int kThreads = 256;
-
-struct HL {  // device copy of fetode_hlogistic_t
-  int in, nb;
-  const float *k, *Ec, *Ps, *bias;
-  float gs, bp;
-};
-
-__device__ __forceinline__ float ref_sigmoid(float z) { return 1.0f / (1.0f + expf(-z)); }
-
-// The head's fp32 summation order, shared by every kernel that evaluates it: q in [0, F) splits
-// into kHeadParts = 32 consecutive parts of head_part(F) (a multiple of 4) indices; each part P_p
-// is an FMA chain from 0 in increasing q; groups of four add as S_w = (P_4w + P_4w+1) +
-// (P_4w+2 + P_4w+3), and the eight S_w add left to right.  (The resident dopri5 gives each wave
-// one group, a quarter-wave per part, and combines a group with two lane shuffles.)
-constexpr int kHeadParts = 32;
-constexpr int kHeadGroups = kHeadParts / 4;
-__host__ __device__ __forceinline__ int head_part(int F) { return (((F + 3) & ~3) + 4 * kHeadParts - 1) / (4 * kHeadParts) * 4; }
-
-// the reference's up / down / gate for element (i, j) at input x (train_ecg_kan_fet_nn_ode.py:110-121)
-struct HPoint {
-  float su, sd, bs, basis;
-};
-__device__ __forceinline__ HPoint hpoint(const HL& L, float x, float pv, int q) {
-  HPoint p;
-  const float k = L.k[q], Ec = L.Ec[q], Ps = L.Ps[q];
-  p.su = 1.0f / (1.0f + expf(-k * (x - Ec)));
-  p.sd = 1.0f / (1.0f + expf(-k * (x + Ec)));
-  const float up = Ps * p.su * 2.0f - Ps;
-  const float down = Ps * p.sd * 2.0f - Ps;
-  const float g = ref_sigmoid(L.gs * (x - pv));
-  p.bs = g > L.bp ? 1.0f : 0.0f;
-  p.basis = p.bs * up + (1.0f - p.bs) * down + L.bias[q];
-  return p;
-}
 
 __global__ __launch_bounds__(kThreads) void mixer_fwd_kernel(HL L, const float* __restrict__ x, int64_t B,
                                                             const float* __restrict__ prev, int act_sigmoid,
@@ -135,24 +102,6 @@ __global__ void head_gw_kernel(const float* __restrict__ g, const float* __restr
   }
 }
 
-// derivative pieces of element (b, i, j): d basis / d (x, k, Ec, Ps), gb = d loss / d basis
-struct HGrad {
-  float gb, dx, dk, dEc, dPs;
-};
-__device__ __forceinline__ HGrad hgrad(const HL& L, float x, float pv, int q, float gphi, float phi, int act_sigmoid) {
-  const HPoint p = hpoint(L, x, pv, q);
-  HGrad r;
-  r.gb = act_sigmoid ? gphi * (phi * (1.0f - phi)) : gphi;
-  const float k = L.k[q], Ec = L.Ec[q], Ps = L.Ps[q];
-  const float cu = p.bs * 2.0f * Ps * p.su * (1.0f - p.su);          // d up / d z_up    (z = k (x - Ec))
-  const float cd = (1.0f - p.bs) * 2.0f * Ps * p.sd * (1.0f - p.sd);  // d down / d z_down (z = k (x + Ec))
-  r.dx = (cu + cd) * k;
-  r.dk = cu * (x - Ec) + cd * (x + Ec);
-  r.dEc = (cd - cu) * k;
-  r.dPs = p.bs * (2.0f * p.su - 1.0f) + (1.0f - p.bs) * (2.0f * p.sd - 1.0f);
-  return r;
-}
-
 __global__ void mixer_gx_kernel(HL L, const float* __restrict__ x, int64_t B, const float* __restrict__ prev,
                                 const float* __restrict__ gphi, const float* __restrict__ phi, int act_sigmoid,
                                 float* __restrict__ gx) {
@@ -190,26 +139,6 @@ __global__ void mixer_gparam_kernel(HL L, const float* __restrict__ x, int64_t B
   if (gEc) gEc[q] = sE;
   if (gPs) gPs[q] = sP;
   if (gbias) gbias[q] = sb;
-}
-
-int check_layer(const fetode_hlogistic_t* l) {
-  if (!l || l->in_dim <= 0 || l->num_basis <= 0) return set_err(FETODE_EINVAL, "hlogistic: bad dims");
-  if (!l->k || !l->Ec || !l->Ps || !l->bias) return set_err(FETODE_EINVAL, "hlogistic: null parameter");
-  return FETODE_OK;
-}
-
-HL to_dev(const fetode_hlogistic_t* l) {
-  HL L;
-  L.in = l->in_dim;
-  L.nb = l->num_basis;
-  L.k = l->k;
-  L.Ec = l->Ec;
-  L.Ps = l->Ps;
-  L.bias = l->bias;
-  // gate_slope * dx with gate_slope a Python float: torch scales an fp32 tensor by it in fp32
-  L.gs = (float)l->gate_slope;
-  L.bp = (float)l->breaking_point;
-  return L;
 }
 
 }  // namespace
@@ -305,14 +234,7 @@ int fetode_hlogistic_mixer_backward(const fetode_hlogistic_t* layer, const float
 // =============================================================================================
 namespace {
 
-constexpr int kMaxF = 768;          // in * num_basis (in <= 64, num_basis <= 12)
 constexpr int kLdsBytes = 163840;   // gfx950: one workgroup may declare all 160 KiB
-
-struct DopriTab {
-  float beta[6][6];  // torchdiffeq Dopri5 tableau rounded to fp32 (tableau.to(y0.dtype))
-  float cerr[7];
-  float cmid[7];
-};
 
 struct EcgDopriArgs {
   HL L;
@@ -342,6 +264,13 @@ struct EcgDopriArgs {
   int max_att;
   long long* stamps;  // debug (fetode_debug_ecg_stamps): workgroup 0's 100 MHz ticks per phase
 };
+// training (fetode_ecg_dopri5_tape): per evaluation e < tape_cap its input x_e and output k_e,
+// tape (tape_cap, 2, B, D); the initial-step scalars {d0, d1, d2, h0, h1}
+struct EcgTapeArgs : EcgDopriArgs {
+  float* tape;
+  int tape_cap;
+  double* init_rec;
+};
 
 // phase timer of workgroup 0 in the diagnostic build only (make stamps, tools/diag/ecg_time.py):
 // other, features, head, partials, norms in 100 MHz ticks; the kernel's s_memtime total
@@ -360,66 +289,6 @@ struct EcgDopriArgs {
   } while (0)
 #endif
 
-__device__ __forceinline__ float fast_sigmoid(float z) { return rcp(1.0f + ex2(-z * FETODE_LOG2E)); }
-
-// Grid barrier, XCD-hierarchical (MI355X_MICROARCH.md "barrier-xcd"): workgroup i runs on XCD
-// i % 8, so each XCD's workgroups arrive on their own counter (256 B apart); the last arriver of an
-// XCD arrives on the top counter, the last of those bumps the generation every workgroup polls.
-// The only data shared across workgroups (the partial slots) moves through agent-scope atomics,
-// coherent across the XCDs' L2s by themselves, so the ordering needed is a vector-memory wait
-// before arriving and after the poll — not agent-scope fences, which would also write back and
-// invalidate the whole L2 (buffer_wbl2 / buffer_inv sc1) at every barrier (fetode_fused.hip
-// dp_order).  Counters reset themselves; the words are zeroed once per launch.
-constexpr int kBarWords = 64 * 10;  // 8 XCD counters, top counter, generation (256 B each)
-// Every spin is bounded (MI355X_MICROARCH.md: a stranded workgroup must not hang the device): after
-// 2^20 polls (about a second) the barrier gives up and raises the abort word 64*9+1.  Once that word
-// is set every barrier returns at once (entering or spinning) and reports it: the solver then stops
-// (status 4) instead of running on with counters that were never reset.
-constexpr unsigned kSpinLimit = 1u << 20;
-__device__ bool grid_barrier(unsigned* bar, unsigned nblk) {
-  __shared__ int s_abort;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const unsigned x = blockIdx.x & 7u;
-    const unsigned nx = (nblk + 7u - x) / 8u, nxcd = nblk < 8u ? nblk : 8u;
-    unsigned* cnt = bar + 64 * x;
-    unsigned* top = bar + 64 * 8;
-    unsigned* gen = bar + 64 * 9;
-    unsigned* abort_word = gen + 1;
-    int ab = __hip_atomic_load(abort_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
-    if (!ab) {
-      const unsigned g = __hip_atomic_load(gen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the slot stores have landed
-      if (__hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == nx - 1u) {
-        __hip_atomic_store(cnt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // reset lands before the release
-        if (__hip_atomic_fetch_add(top, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == nxcd - 1u) {
-          __hip_atomic_store(top, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-          __hip_atomic_fetch_add(gen, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-      }
-      unsigned spins = 0;
-      while (__hip_atomic_load(gen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == g) {
-        __builtin_amdgcn_s_sleep(1);
-        if (__hip_atomic_load(abort_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
-          ab = 1;
-          break;
-        }
-        if (++spins == kSpinLimit) {
-          __hip_atomic_store(abort_word, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          ab = 1;
-          break;
-        }
-      }
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    s_abort = ab;
-  }
-  __syncthreads();
-  return s_abort != 0;
-}
-
 // NT = 512 threads, R rows per workgroup (R-1 real + the shadow).  Solver thread (r, d) = tid for
 // tid < 64 R carries state element d of row r.
 // Features: the R * F (row, basis) elements of an evaluation are dealt round-robin to all threads
@@ -430,9 +299,11 @@ __device__ bool grid_barrier(unsigned* bar, unsigned nblk) {
 // forms the part's sums for outputs l16 + 16c (c < 4) of every row.  The part's W^T rows sit in
 // LDS as [part][q/4][64] float4 (the first QL) and in registers (the rest, <= TAIL).  Two lane
 // shuffles combine the four parts of a group; the solver threads add the eight groups.
+// TAPE: the same arithmetic, and every evaluation's input / output, the initial-step scalars and
+// (as always) the attempt log written out for the reverse sweep (fetode_ecg_bwd.hip).
 constexpr int kResThreads = 512;
-template <int R, int TAIL>
-__global__ __launch_bounds__(kResThreads) void ecg_dopri5_kernel(EcgDopriArgs a) {
+template <int R, int TAIL, bool TAPE, class Args>
+__device__ __forceinline__ void ecg_dopri5_body(const Args& a) {
   constexpr int NT = kResThreads, NR = R - 1, EPT = (R * kMaxF + NT - 1) / NT;
   constexpr int FU = R <= 4 ? EPT : 2;  // feature-loop unroll (R = 8: registers)
   static_assert(NT / 64 == kHeadGroups, "one head group per wave");
@@ -555,6 +426,9 @@ __global__ __launch_bounds__(kResThreads) void ecg_dopri5_kernel(EcgDopriArgs a)
   // one field evaluation of the solver thread's element; every thread of the workgroup takes part
   auto eval = [&](float xv) -> float {
     if (dval) xs[r][d] = xv;
+    if constexpr (TAPE) {
+      if (real && nfev < a.tape_cap) a.tape[(int64_t)nfev * 2 * BD + b * D + d] = xv;
+    }
     __syncthreads();
     STAMP(0);
     const int n = nfev;
@@ -651,6 +525,9 @@ __global__ __launch_bounds__(kResThreads) void ecg_dopri5_kernel(EcgDopriArgs a)
       for (int w = 1; w < kHeadGroups; ++w) out = out + hs[(w * R + r) * 64 + d];
       out = out + bhd;
     }
+    if constexpr (TAPE) {
+      if (real && nfev < a.tape_cap) a.tape[((int64_t)nfev * 2 + 1) * BD + b * D + d] = out;
+    }
     // no trailing barrier: the next evaluation writes xs, then waits before phi / hs are rewritten
     ++nfev;
     return out;
@@ -680,6 +557,15 @@ __global__ __launch_bounds__(kResThreads) void ecg_dopri5_kernel(EcgDopriArgs a)
     if (d1 <= 1e-15f && d2 <= 1e-15f) h1 = fmaxf(1e-6f, h0 * 1e-3f);
     else h1 = (float)pow((double)(0.01f / fmaxf(d1, d2)), (double)0.2f);  // fp64 pow rounded once: host == device
     dt = (double)fminf(100.0f * h0, fabsf(h1));
+    if constexpr (TAPE) {
+      if (blockIdx.x == 0 && tid == 0 && a.init_rec) {
+        a.init_rec[0] = d0;
+        a.init_rec[1] = d1;
+        a.init_rec[2] = d2;
+        a.init_rec[3] = h0;
+        a.init_rec[4] = h1;
+      }
+    }
   }
 
   float co[5] = {y, 0.f, 0.f, 0.f, 0.f};
@@ -795,6 +681,16 @@ __global__ __launch_bounds__(kResThreads) void ecg_dopri5_kernel(EcgDopriArgs a)
   }
 }
 
+template <int R, int TAIL>
+__global__ __launch_bounds__(kResThreads) void ecg_dopri5_kernel(EcgDopriArgs a) {
+  ecg_dopri5_body<R, TAIL, false, EcgDopriArgs>(a);
+}
+// the taped solve under a name of its own: the inference kernels keep their code and resources
+template <int R, int TAIL>
+__global__ __launch_bounds__(kResThreads) void ecg_dopri5_tape_kernel(EcgTapeArgs a) {
+  ecg_dopri5_body<R, TAIL, true, EcgTapeArgs>(a);
+}
+
 long long* g_ecg_stamps = nullptr;  // fetode_debug_ecg_stamps
 
 // one instantiation of the resident kernel: rows per workgroup and the register tail per part
@@ -802,29 +698,32 @@ struct EcgVariant {
   const void* fn;
   int rows, tail;
 };
-const EcgVariant kEcgVariants[] = {
-    {reinterpret_cast<const void*>(ecg_dopri5_kernel<4, 8>), 4, 8},
-    {reinterpret_cast<const void*>(ecg_dopri5_kernel<8, 8>), 8, 8},
+constexpr int kNumEcgVariants = 2;
+const EcgVariant kEcgVariants[2][kNumEcgVariants] = {
+    {{reinterpret_cast<const void*>(ecg_dopri5_kernel<4, 8>), 4, 8},
+     {reinterpret_cast<const void*>(ecg_dopri5_kernel<8, 8>), 8, 8}},
+    {{reinterpret_cast<const void*>(ecg_dopri5_tape_kernel<4, 8>), 4, 8},
+     {reinterpret_cast<const void*>(ecg_dopri5_tape_kernel<8, 8>), 8, 8}},
 };
 
-}  // namespace
-
-extern "C" {
-
-int fetode_ecg_dopri5(const fetode_hlogistic_t* layer, const float* wT, const float* bias, int32_t D,
-                      const float* prev, const float* y0, int64_t B, const double* t, int32_t T, double rtol,
-                      double atol, const double* opts, const float* tableau, float* solution, float* prev_out,
-                      float* branch_out, void* workspace, int32_t* stats, double* attempts, int32_t max_attempts,
-                      void* stream) {
+// fetode_ecg_dopri5 (taped = false) and fetode_ecg_dopri5_tape: the same checks, grid choice and
+// launch; every refusal comes before the launch, so no state is touched
+int ecg_dopri5_impl(const fetode_hlogistic_t* layer, const float* wT, const float* bias, int32_t D,
+                    const float* prev, const float* y0, int64_t B, const double* t, int32_t T, double rtol,
+                    double atol, const double* opts, const float* tableau, float* solution, float* prev_out,
+                    float* branch_out, void* workspace, int32_t* stats, double* attempts, int32_t max_attempts,
+                    bool taped, float* tape, int32_t tape_cap, double* init_rec, void* stream) {
   int rc = check_layer(layer);
   if (rc) return rc;
   if (B <= 0 || T <= 0) return FETODE_OK;
   if (!wT || !prev || !y0 || !t || !opts || !tableau || !solution || !prev_out || !workspace || !stats)
     return set_err(FETODE_EINVAL, "ecg dopri5: null pointer");
+  if (taped && (!tape || tape_cap < 0 || !init_rec || !attempts))
+    return set_err(FETODE_EINVAL, "ecg dopri5 tape: null tape / init_rec / attempts or negative capacity");
   if (D != layer->in_dim || D > 64) return set_err(FETODE_EINVAL, "ecg dopri5: state dim %d (must equal in_dim, <= 64)", D);
   const int F = layer->in_dim * layer->num_basis;
   if (F > kMaxF) return set_err(FETODE_EUNSUPPORTED, "ecg dopri5: in*num_basis=%d > %d", F, kMaxF);
-  EcgDopriArgs a;
+  EcgTapeArgs a;  // the untaped kernels take its EcgDopriArgs part
   memset(&a, 0, sizeof(a));
   a.L = to_dev(layer);
   a.wT = wT;
@@ -856,6 +755,9 @@ int fetode_ecg_dopri5(const fetode_hlogistic_t* layer, const float* wT, const fl
   a.att = attempts;
   a.max_att = attempts ? max_attempts : 0;
   a.stamps = g_ecg_stamps;
+  a.tape = tape;
+  a.tape_cap = taped ? tape_cap : 0;
+  a.init_rec = init_rec;
   // per-variant launch facts, queried once (static LDS, the dynamic-LDS cap) and per LDS size
   // (occupancy): the launch path does no runtime queries on repeat calls
   static int n_cu_of[64] = {0};
@@ -863,7 +765,7 @@ int fetode_ecg_dopri5(const fetode_hlogistic_t* layer, const float* wT, const fl
     int static_lds = -1;
     size_t lds = 0;
     int per_cu = 0;
-  } vstate[sizeof(kEcgVariants) / sizeof(kEcgVariants[0])];
+  } vstate_all[2][kNumEcgVariants];
   int dev = 0;
   HIP_CHECK_RET(hipGetDevice(&dev));
   if (dev < 0 || dev >= 64) return set_err(FETODE_EINVAL, "ecg dopri5: device %d", dev);
@@ -872,9 +774,9 @@ int fetode_ecg_dopri5(const fetode_hlogistic_t* layer, const float* wT, const fl
   a.PS = head_part(F);
   // the smallest workgroup whose grid is co-resident (one cooperative grid) and whose head
   // weight fits LDS + its register tail
-  for (size_t vi = 0; vi < sizeof(kEcgVariants) / sizeof(kEcgVariants[0]); ++vi) {
-    const EcgVariant& v = kEcgVariants[vi];
-    auto& vs = vstate[vi];
+  for (int vi = 0; vi < kNumEcgVariants; ++vi) {
+    const EcgVariant& v = kEcgVariants[taped ? 1 : 0][vi];
+    auto& vs = vstate_all[taped ? 1 : 0][vi];
     if (vs.static_lds < 0) {
       hipFuncAttributes fa;
       HIP_CHECK_RET(hipFuncGetAttributes(&fa, v.fn));
@@ -902,12 +804,34 @@ int fetode_ecg_dopri5(const fetode_hlogistic_t* layer, const float* wT, const fl
     a.QL = QL;
     hipStream_t s = (hipStream_t)stream;
     HIP_CHECK_RET(hipMemsetAsync(workspace, 0, sizeof(unsigned) * kBarWords, s));
-    void* args[] = {&a};
+    void* args[] = {taped ? (void*)&a : (void*)static_cast<EcgDopriArgs*>(&a)};
     HIP_CHECK_RET(resident_launch(v.fn, dim3((unsigned)grid), dim3(kResThreads), args, lds, s));
     return FETODE_OK;
   }
   return set_err(FETODE_EUNSUPPORTED, "ecg dopri5: batch %lld x in*num_basis %d does not fit one resident grid",
                  (long long)B, F);
+}
+
+}  // namespace
+
+extern "C" {
+
+int fetode_ecg_dopri5(const fetode_hlogistic_t* layer, const float* wT, const float* bias, int32_t D,
+                      const float* prev, const float* y0, int64_t B, const double* t, int32_t T, double rtol,
+                      double atol, const double* opts, const float* tableau, float* solution, float* prev_out,
+                      float* branch_out, void* workspace, int32_t* stats, double* attempts, int32_t max_attempts,
+                      void* stream) {
+  return ecg_dopri5_impl(layer, wT, bias, D, prev, y0, B, t, T, rtol, atol, opts, tableau, solution, prev_out,
+                         branch_out, workspace, stats, attempts, max_attempts, false, nullptr, 0, nullptr, stream);
+}
+
+int fetode_ecg_dopri5_tape(const fetode_hlogistic_t* layer, const float* wT, const float* bias, int32_t D,
+                           const float* prev, const float* y0, int64_t B, const double* t, int32_t T, double rtol,
+                           double atol, const double* opts, const float* tableau, float* solution, float* prev_out,
+                           float* branch_out, void* workspace, int32_t* stats, double* attempts,
+                           int32_t max_attempts, float* tape, int32_t tape_cap, double* init_rec, void* stream) {
+  return ecg_dopri5_impl(layer, wT, bias, D, prev, y0, B, t, T, rtol, atol, opts, tableau, solution, prev_out,
+                         branch_out, workspace, stats, attempts, max_attempts, true, tape, tape_cap, init_rec, stream);
 }
 
 #ifdef FETODE_STAMPS

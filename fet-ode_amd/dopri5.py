@@ -686,6 +686,151 @@ def _try_field_resident_train(func, y0, tp, reversed_, rtol, atol, options):
                                 _opts_array(options), *params)
 
 
+class _EcgDeclined(Exception):
+    """fetode_ecg_dopri5_tape refused the launch (FETODE_EUNSUPPORTED, nothing written)."""
+
+
+class _EcgDopri5Fn(torch.autograd.Function):
+    """Training through the device-resident dopri5 solve of the ECG field (the reference's own
+    training call: odeint(self.odefunc, h0, [0, 1], method="dopri5") then loss.backward(),
+    train_ecg_kan_fet_nn_ode.py:551-572, :575-617).  Forward: ONE launch (fetode_ecg_dopri5_tape)
+    that also records every evaluation's input and output, the attempt log and the initial-step
+    scalars; the tape is sized from the module's previous solve, and a longer solve is re-run from
+    the saved prev_x with a larger one.  Backward: ONE resident launch that walks the attempts
+    backwards (fetode_ecg_dopri5_backward) plus the parameter sums over the stacked evaluations."""
+
+    @staticmethod
+    def forward(ctx, func, y0, t_dev, rtol, atol, opts, w, b, k, Ec, Ps, bias):
+        lib = _lib.load()
+        basis = func.feat.basis
+        dev = y0.device
+        B, D = y0.shape
+        T = t_dev.numel()
+        pk, pEc, pPs, pbias = (_lib.f32c(p.detach()) for p in (k, Ec, Ps, bias))
+        d = _lib.HLogisticDesc(basis.in_dim, basis.num_basis, pk.data_ptr(), pEc.data_ptr(), pPs.data_ptr(),
+                               pbias.data_ptr(), float(basis.gate_slope), float(basis.branch_breaking_point))
+        wc = _lib.f32c(w.detach())
+        wT = wc.t().contiguous()
+        bc = _lib.f32c(b.detach()) if b is not None else None
+        prev = basis._prev_for(dev)
+        prev0 = prev.clone()   # the reverse sweep's first memory; restored before a re-run / on a timeout
+        cap, max_att = getattr(func, "_fetode_d5tape", (256, 64))
+        cap, max_att = max(1, int(cap)), max(1, int(max_att))
+        sol = torch.empty(T, B, D, device=dev, dtype=torch.float32)
+        branch = torch.empty(B, basis.in_dim, basis.num_basis, device=dev, dtype=torch.float32)
+        ws = torch.empty(max(1, lib.fetode_ecg_dopri5_workspace(B) // 4), device=dev, dtype=torch.float32)
+        stats = torch.empty(3, device=dev, dtype=torch.int32)
+        init_rec = torch.zeros(5, device=dev, dtype=torch.float64)
+        optp = opts.ctypes.data_as(_lib.ctypes.POINTER(_lib.ctypes.c_double))
+        tabp = _TABLEAU.ctypes.data_as(_lib.ctypes.POINTER(_lib.ctypes.c_float))
+        while True:
+            tape = torch.empty(cap, 2, B, D, device=dev, dtype=torch.float32)   # x_e, k_e per evaluation
+            att = torch.empty(max_att, 4, device=dev, dtype=torch.float64)
+            rc = lib.fetode_ecg_dopri5_tape(
+                _lib.ctypes.byref(d), wT.data_ptr(), _lib.ptr(bc), D, prev.data_ptr(), y0.data_ptr(), B,
+                t_dev.data_ptr(), T, rtol, atol, optp, tabp, sol.data_ptr(), prev.data_ptr(), branch.data_ptr(),
+                ws.data_ptr(), stats.data_ptr(), att.data_ptr(), max_att, tape.data_ptr(), cap, init_rec.data_ptr(),
+                _lib.stream_handle(dev))
+            if rc == _lib.FETODE_EUNSUPPORTED:
+                raise _EcgDeclined()
+            _lib.check(rc, "fetode_ecg_dopri5_tape")
+            nfev, n_att, status = stats.tolist()
+            if status == 4:
+                prev.copy_(prev0)   # a grid timeout leaves the pre-solve memory (as the inference path)
+            _raise_status(status, "fetode_ecg_dopri5_tape: a grid barrier timed out (workgroups not co-resident); "
+                                  "the solution is invalid")
+            if nfev <= cap and n_att <= max_att:
+                break
+            prev.copy_(prev0)   # the tape ran out: the same solve again with room for all of it
+            cap, max_att = nfev + 12, n_att + 2
+        func._fetode_d5tape = (nfev + max(12, nfev // 8), n_att + max(2, n_att // 8))
+        basis.branch_state = branch
+        dopri5_solve.last = ResidentSolve(stats, att)
+        ctx.basis, ctx.B, ctx.D = basis, B, D
+        ctx.t_dev, ctx.rtol, ctx.atol, ctx.opts = t_dev, rtol, atol, opts
+        ctx.n_ev, ctx.n_att, ctx.has_b = nfev, n_att, b is not None
+        ctx.save_for_backward(tape, att, init_rec, prev0, wc, pk, pEc, pPs, pbias)
+        return sol
+
+    @staticmethod
+    def backward(ctx, grad):
+        lib = _lib.load()
+        tape, att, init_rec, prev0, wc, pk, pEc, pPs, pbias = ctx.saved_tensors
+        basis, B, D = ctx.basis, ctx.B, ctx.D
+        dev = grad.device
+        d = _lib.HLogisticDesc(basis.in_dim, basis.num_basis, pk.data_ptr(), pEc.data_ptr(), pPs.data_ptr(),
+                               pbias.data_ptr(), float(basis.gate_slope), float(basis.branch_breaking_point))
+        g = _lib.f32c(grad)
+        want = ctx.needs_input_grad
+
+        def buf(i, *shape):
+            return torch.empty(*shape, device=dev, dtype=torch.float32) if want[i] else None
+
+        gy0 = buf(1, B, D)
+        gw = buf(6, *wc.shape)
+        gbh = buf(7, D) if ctx.has_b else None
+        gp = [buf(8 + i, basis.in_dim, basis.num_basis) for i in range(4)]
+        nbytes = lib.fetode_ecg_dopri5_backward_workspace(_lib.ctypes.byref(d), B, ctx.n_ev)
+        if nbytes < 0:
+            _lib.check(_lib.FETODE_EUNSUPPORTED, "fetode_ecg_dopri5_backward_workspace")
+        ws = torch.empty(max(1, nbytes // 4), device=dev, dtype=torch.float32)
+        status = torch.empty(1, device=dev, dtype=torch.int32)
+        _lib.check(lib.fetode_ecg_dopri5_backward(
+            _lib.ctypes.byref(d), wc.data_ptr(), D, prev0.data_ptr(), B, ctx.t_dev.data_ptr(), ctx.t_dev.numel(),
+            ctx.rtol, ctx.atol, ctx.opts.ctypes.data_as(_lib.ctypes.POINTER(_lib.ctypes.c_double)),
+            _TABLEAU.ctypes.data_as(_lib.ctypes.POINTER(_lib.ctypes.c_float)), g.data_ptr(), tape.data_ptr(),
+            ctx.n_ev, att.data_ptr(), ctx.n_att, init_rec.data_ptr(), _lib.ptr(gy0), _lib.ptr(gw), _lib.ptr(gbh),
+            *[_lib.ptr(t) for t in gp], ws.data_ptr(), status.data_ptr(), _lib.stream_handle(dev)),
+            "fetode_ecg_dopri5_backward")
+        _raise_status(int(status.item()), "fetode_ecg_dopri5_backward: a grid sum timed out (workgroups not "
+                                          "co-resident); the gradients are invalid")
+        return (None, gy0, None, None, None, None, gw, gbh, *gp)
+
+
+_ECG_RESIDENT_TRAIN = os.environ.get("FETODE_ECG_DOPRI5_TAPE", "0") == "1"
+
+
+def set_resident_ecg_training(enabled: bool) -> bool:
+    """Route dopri5 training solves of the ECG field (No_MLP_KANODEFunc) through the taped resident
+    solve + resident reverse sweep, or (default) through _Dopri5Grad (host-driven autograd).  Also
+    env FETODE_ECG_DOPRI5_TAPE=1.  Returns the previous value."""
+    global _ECG_RESIDENT_TRAIN
+    prev, _ECG_RESIDENT_TRAIN = _ECG_RESIDENT_TRAIN, bool(enabled)
+    return prev
+
+
+def _try_ecg_resident_train(func, y0, tp, reversed_, rtol, atol, options):
+    """The taped resident solve + reverse sweep when `func` is the ECG field with the sigmoid mixer,
+    something needs gradients, the solve is forward in time, the options and tolerances are the
+    scalar ones and the batch fits both resident grids; None otherwise (the caller's host path)."""
+    from .ecg import No_MLP_KANODEFunc
+    import torch.nn as nn
+    if not isinstance(func, No_MLP_KANODEFunc) or reversed_ or y0.dim() != 2:
+        return None
+    if not isinstance(func.feat.act, nn.Sigmoid) or set(options) - _RESIDENT_OPTS:
+        return None
+    if not (isinstance(rtol, (int, float)) and isinstance(atol, (int, float))):
+        return None
+    basis = func.feat.basis
+    B, D = y0.shape
+    if D != basis.in_dim or D > 64 or B > 3072 or func.proj.out_features != D or basis.use_noise or B <= 0:
+        return None
+    if basis.in_dim * basis.num_basis > 768:
+        return None
+    lib = _lib.load()
+    keep = []
+    d = basis.desc(keep)
+    if B > lib.fetode_ecg_dopri5_backward_max_batch(_lib.ctypes.byref(d)):
+        return None
+    dev = y0.device
+    try:
+        return _EcgDopri5Fn.apply(func, y0.to(torch.float32).contiguous(), _t_device(tp, dev), float(rtol),
+                                  float(atol), _opts_array(options), func.proj.weight, func.proj.bias, basis.k,
+                                  basis.Ec, basis.Ps, basis.bias)
+    except _EcgDeclined:
+        return None
+
+
 def _try_wide_resident(func, y0, tp, reversed_, rtol, atol, options):
     """The whole solve in one launch (fetode_wide_dopri5) when `func` is a tagged two-layer wide
     KAN-FET field — the ETT forecaster's KANFETDynamics, KANFET([latent, hidden, latent]),
@@ -1176,6 +1321,10 @@ def dopri5_solve(func, y0, tc, tp, reversed_, rtol, atol, options):
         if sol is not None:
             return sol
     if _needs_grad(func, y0):
+        if _RESIDENT and _ECG_RESIDENT_TRAIN:
+            sol = _try_ecg_resident_train(func, y0, tp, reversed_, rtol, atol, options)
+            if sol is not None:
+                return sol
         if _RESIDENT and _RESIDENT_TRAIN:
             sol = _try_field_resident_train(func, y0, tp, reversed_, rtol, atol, options)
             if sol is not None:

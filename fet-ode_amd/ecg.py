@@ -21,7 +21,9 @@ The mixer (+ Linear head) is one HIP launch per call (fetode_hlogistic_mixer_for
 VJP; the encoder / classifier Linear layers are plain library GEMMs (torch).  There is no CPU
 path.  Not provided: use_noise=True (random).  Backprop through dopri5 works like torchdiffeq's
 direct backprop (dopri5._Dopri5Grad: every stage, error ratio and step size, with the mixer's HIP
-VJP per evaluation); the device-resident solve serves inference only.
+VJP per evaluation) by default; with dopri5.set_resident_ecg_training(True) (env
+FETODE_ECG_DOPRI5_TAPE=1) a No_MLP_KANODEFunc training solve is the device-resident solve with a tape
+(fetode_ecg_dopri5_tape) and one resident reverse sweep (fetode_ecg_dopri5_backward).
 """
 from __future__ import annotations
 

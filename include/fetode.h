@@ -530,6 +530,48 @@ int fetode_ecg_dopri5(const fetode_hlogistic_t* layer, const float* wT, const fl
                       void* stream);
 int64_t fetode_ecg_dopri5_workspace(int64_t B);
 
+/* Training through that solve (train_ecg_kan_fet_nn_ode.py:551-572 then loss.backward(), :575-617).
+ * fetode_ecg_dopri5_tape: fetode_ecg_dopri5 — the same arithmetic, attempts, solution, prev_out and
+ * branch_out, bit for bit — which also records what the reverse sweep needs:
+ *   tape (dev, (tape_cap, 2, B, D)): per evaluation e < tape_cap its input x_e and output k_e;
+ *   attempts (required here) as above; init_rec (dev, 5 doubles): d0, d1, d2, h0, h1 of
+ *   misc._select_initial_step (untouched with first_step).
+ * stats[0] is always the true number of evaluations: when it exceeds tape_cap (or stats[1] exceeds
+ * max_attempts) the caller restores prev and runs again with a larger tape.  Same limits, grids and
+ * FETODE_EUNSUPPORTED (returned before anything is written) as fetode_ecg_dopri5. */
+int fetode_ecg_dopri5_tape(const fetode_hlogistic_t* layer, const float* wT, const float* bias, int32_t D,
+                           const float* prev, const float* y0, int64_t B, const double* t, int32_t T, double rtol,
+                           double atol, const double* opts, const float* tableau, float* solution, float* prev_out,
+                           float* branch_out, void* workspace, int32_t* stats, double* attempts,
+                           int32_t max_attempts, float* tape, int32_t tape_cap, double* init_rec, void* stream);
+/* The reverse sweep of fetode_ecg_dopri5_tape in ONE resident launch, then the parameter sums in
+ * three ordinary ones.  The sweep walks the attempts backwards (rejected ones included) through the
+ * FSAL carry and the six stage sums, _interp_fit / _interp_evaluate at every output time, the error
+ * ratio, the step-size control (through the factor the forward took, read from the attempt log),
+ * _select_initial_step and its probe; the adjoint of dt couples the batch: one fixed-order fp64 grid
+ * sum per attempt.  The hysteresis branch of every element is recomputed from the tape with the
+ * forward's expression (the memory of evaluation e is row B-1 of x_{e-1}; prev for e = 0); no
+ * gradient flows through the gate or the memory, as in the reference (:123, :131-132).
+ *   w (D, in*nb) the head weight (not transposed); prev (in*nb) prev_x BEFORE the solve; t, T,
+ *   rtol, atol, opts, tableau as the forward's; grad_solution (T, B, D); tape with n_ev
+ *   evaluations, attempts with n_att rows, init_rec: the forward's (n_ev must equal
+ *   (opts[0] > 0 ? 1 : 2) + 6 n_att, else FETODE_EINVAL);
+ *   outputs (nullable, written): grad_y0 (B, D), gw (D, in*nb), gbias_head (D), gk / gEc / gPs /
+ *   gbias (in, nb) — all sums in a fixed order, no atomics: run-to-run identical;
+ *   workspace: fetode_ecg_dopri5_backward_workspace(layer, B, n_ev) bytes (< 0: bad arguments);
+ *   status (dev, 1 int): 0, or 4 when a grid barrier timed out (the gradients are invalid).
+ * FETODE_EUNSUPPORTED (before anything is written) when in_dim > 64, in*nb > 768 or B exceeds
+ * fetode_ecg_dopri5_backward_max_batch(layer) (4 rows per workgroup of one co-resident grid; 0: no
+ * resident sweep for this shape, < 0: bad layer or no device). */
+int64_t fetode_ecg_dopri5_backward_max_batch(const fetode_hlogistic_t* layer);
+int64_t fetode_ecg_dopri5_backward_workspace(const fetode_hlogistic_t* layer, int64_t B, int32_t n_ev);
+int fetode_ecg_dopri5_backward(const fetode_hlogistic_t* layer, const float* w, int32_t D, const float* prev,
+                               int64_t B, const double* t, int32_t T, double rtol, double atol, const double* opts,
+                               const float* tableau, const float* grad_solution, const float* tape, int32_t n_ev,
+                               const double* attempts, int32_t n_att, const double* init_rec, float* grad_y0,
+                               float* gw, float* gbias_head, float* gk, float* gEc, float* gPs, float* gbias,
+                               void* workspace, int32_t* status, void* stream);
+
 /* Elementwise stages of the ECG FerroElectricNet field KANFetODEFunc (train_ecg.py:986-1013; the
  * two FerroelectricBasis layers are fetode_ferro_forward / _backward), in torch's op order:
  *   fetode_tanh_bound: out = h_bound * tanh(x / h_bound) (:1002); t_out (nullable) keeps the tanh
