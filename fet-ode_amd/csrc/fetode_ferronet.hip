@@ -56,7 +56,8 @@ __global__ __launch_bounds__(kThreadsEw) void nan_clamp_kernel(int64_t n, float 
                                                               float* __restrict__ out) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
     const float v = nan_to_num(x[i], nan, posinf, neginf);
-    out[i] = fminf(fmaxf(v, lo), hi);
+    // torch.clamp propagates NaN (fminf / fmaxf would return the bound): a NaN replacement stays NaN
+    out[i] = __builtin_isnan(v) ? v : fminf(fmaxf(v, lo), hi);
   }
 }
 
@@ -66,8 +67,10 @@ __global__ __launch_bounds__(kThreadsEw) void nan_clamp_bwd_kernel(int64_t n, fl
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
     const float xv = x[i];
     const float v = nan_to_num(xv, nan, posinf, neginf);
-    const bool pass = __builtin_isfinite(xv) && v >= lo && v <= hi;
-    gx[i] = pass ? g[i] : 0.0f;
+    // autograd's two factors in its order: clamp' selects (g or +0), nan_to_num' multiplies by
+    // isfinite(x) — so a masked non-finite x gives g * 0 (the sign of g, NaN for a non-finite g)
+    const float c = (v >= lo && v <= hi) ? g[i] : 0.0f;
+    gx[i] = c * (__builtin_isfinite(xv) ? 1.0f : 0.0f);
   }
 }
 

@@ -577,8 +577,10 @@ int fetode_ecg_dopri5_backward(const fetode_hlogistic_t* layer, const float* w, 
  *   fetode_tanh_bound: out = h_bound * tanh(x / h_bound) (:1002); t_out (nullable) keeps the tanh
  *   for the backward, gx = ((g * h_bound) * (1 - t^2)) / h_bound;
  *   fetode_tanh: nn.Tanh between the layers (:1004), gx = g * (1 - y^2);
- *   fetode_nan_clamp: clamp(nan_to_num(x, nan, posinf, neginf), lo, hi) (:1008-1011),
- *   gx = g where x is finite and lo <= nan_to_num(x) <= hi, else 0. */
+ *   fetode_nan_clamp: clamp(nan_to_num(x, nan, posinf, neginf), lo, hi) (:1008-1011); a NaN
+ *   replacement stays NaN, as torch.clamp propagates it;
+ *   gx = (lo <= nan_to_num(x) <= hi ? g : 0) * isfinite(x), autograd's two factors: g where x is
+ *   finite and inside the clamp, +0 outside it, g * 0 (the sign of g) for a non-finite x. */
 int fetode_tanh_bound(int64_t n, float h_bound, const float* x, float* out, float* t_out, void* stream);
 int fetode_tanh_bound_backward(int64_t n, float h_bound, const float* g, const float* t, float* gx, void* stream);
 int fetode_tanh(int64_t n, const float* x, float* out, void* stream);

@@ -463,7 +463,7 @@ class _UncheckedAssign(torch.autograd.Function):
 
 
 def _dopri5(func, y0, t, rtol, atol, trace: Optional[Dopri5Trace], max_num_steps=2 ** 31 - 1,
-            first_step=None, replay=None):
+            first_step=None, replay=None, safety=0.9, ifactor=10.0, dfactor=0.2):
     """RKAdaptiveStepsizeODESolver + Dopri5Solver (rk_common.py / dopri5.py).
 
     ``replay``: a list of (t0, dt, accepted) attempts recorded by another solve of the same batch
@@ -478,9 +478,9 @@ def _dopri5(func, y0, t, rtol, atol, trace: Optional[Dopri5Trace], max_num_steps
     tdt = torch.promote_types(torch.float64, sdt)
     rtol_t = torch.as_tensor(rtol, dtype=tdt)
     atol_t = torch.as_tensor(atol, dtype=tdt)
-    safety = torch.as_tensor(0.9, dtype=tdt)
-    ifactor = torch.as_tensor(10.0, dtype=tdt)
-    dfactor0 = torch.as_tensor(0.2, dtype=tdt)
+    safety = torch.as_tensor(safety, dtype=tdt)
+    ifactor = torch.as_tensor(ifactor, dtype=tdt)
+    dfactor0 = torch.as_tensor(dfactor, dtype=tdt)
     alpha = torch.tensor(DOPRI5_ALPHA, dtype=torch.float64).to(sdt)
     beta = [torch.tensor(b_, dtype=torch.float64).to(sdt) for b_ in DOPRI5_BETA]
     c_err = torch.tensor(DOPRI5_C_ERR, dtype=torch.float64).to(sdt)
@@ -565,8 +565,10 @@ def odeint(func: Callable, y0: torch.Tensor, t, *, rtol=1e-7, atol=1e-9, method=
     options = dict(options or {})
     func, t, method, reversed_ = _check_inputs(func, y0, t, method)
     if method == "dopri5":
+        # max_num_steps / safety / ifactor / dfactor: torchdiffeq's Dopri5Solver constructor arguments
+        ctrl = {k_: options[k_] for k_ in ("max_num_steps", "safety", "ifactor", "dfactor") if k_ in options}
         sol = _dopri5(func, y0, t, rtol, atol, trace, first_step=options.get("first_step"),
-                      replay=options.get("replay"))
+                      replay=options.get("replay"), **ctrl)
     else:
         step = {"euler": euler_step, "midpoint": midpoint_step, "rk4_classic": rk4_classic_step,
                 "rk4": rk4_classic_step if classic_rk4 else rk4_alt_step}[method]
