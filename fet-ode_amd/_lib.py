@@ -110,6 +110,10 @@ SIGNATURES = {
     "fetode_fused_set_v8_tpb": (ctypes.c_int, [ctypes.c_int]),
     "fetode_fused_get_batch_ranges": (ctypes.c_int, [ctypes.c_void_p]),
     "fetode_dopri5_set_spin_limit": (ctypes.c_uint32, [ctypes.c_uint32]),
+    "fetode_dopri5_set_multipass": (ctypes.c_int, [ctypes.c_int]),
+    "fetode_dopri5_set_grid_limit": (ctypes.c_int64, [ctypes.c_int64]),
+    "fetode_integrate_dopri5_multipass_max_batch": (ctypes.c_int64, [ctypes.POINTER(FieldDesc)]),
+    "fetode_integrate_dopri5_backward_set_shape": (ctypes.c_int, [ctypes.c_int]),
     "fetode_integrate_dopri5": (ctypes.c_int, [ctypes.POINTER(FieldDesc), _vp, _vp, ctypes.c_int64, _vp,
                                                ctypes.c_int32, ctypes.c_double, ctypes.c_double,
                                                ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_float), _vp,

@@ -41,575 +41,7 @@ namespace {
 
 #include "fetode_gridsum.h"
 
-constexpr int kSO = 3;  // spline order of the fused kernels (efficientkan default)
-// FETODE_EXP_SKIP (phase-cost attribution: 1 Ferro, 2 edges, 4 logistic, 8 features, 16 d/dx
-// reductions compiled out — results are wrong when set) exists only in the diagnostic build
-// (make diag EXTRA=-DFETODE_EXP_SKIP=n); the product library is always built with 0.
-#if defined(FETODE_EXP_SKIP) && !defined(FETODE_DIAG)
-#error "FETODE_EXP_SKIP is a diagnostic knob: build it with make diag"
-#endif
-#ifndef FETODE_EXP_SKIP
-#define FETODE_EXP_SKIP 0
-#endif
-
-typedef float f2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ f2 pfma(f2 a, f2 b, f2 c) { return __builtin_elementwise_fma(a, b, c); }
-__device__ __forceinline__ f2 splat(float v) { return f2{v, v}; }
-__device__ __forceinline__ f2 ex2x2(f2 v) { return f2{ex2(v.x), ex2(v.y)}; }
-__device__ __forceinline__ f2 rcpx2(f2 v) { return f2{rcp(v.x), rcp(v.y)}; }
-
-constexpr int pow2_floor(int v) {
-  int p = 1;
-  while (p * 2 <= v) p *= 2;
-  return p;
-}
-
-// Layout of one layer's gradient sums in a partial row (host and device agree on it).
-struct AccLayout {
-  int E, NE, NL, NS, NTM;
-  int oA, oC, oE, oG, oBase, oSpl, oLw, oLa, oLb, n;
-};
-__host__ __device__ constexpr AccLayout acc_layout(int in, int out, int K, int NB, int NS, bool ferro) {
-  AccLayout L{};
-  L.E = ferro ? in * out * K : 0;
-  L.NE = in * out;
-  L.NL = in * NB;
-  L.NS = NS;
-  L.NTM = (ferro ? out * K : 0) + out + NB;
-  L.oA = 0;
-  L.oC = L.E;
-  L.oE = 2 * L.E;
-  L.oG = 3 * L.E;
-  L.oBase = L.oG + (ferro ? out : 0);
-  L.oSpl = L.oBase + L.NE;
-  L.oLw = L.oSpl + L.NE * NS;
-  L.oLa = L.oLw + out * L.NL;
-  L.oLb = L.oLa + L.NL;
-  L.n = L.oLb + L.NL;
-  return L;
-}
-
-template <int IN_, int OUT_, int K_, int NB_, int NG_, bool FERRO_>
-struct BL {  // compile-time shape of one layer
-  static constexpr int IN = IN_, OUT = OUT_, K = FERRO_ ? K_ : 0, NB = NB_, NG = NG_;
-  static constexpr bool FERRO = FERRO_;
-  static constexpr int NI = NG - 1, NS = NG - 1 - kSO, NFL = 1 + NB;
-  static constexpr AccLayout AL = acc_layout(IN, OUT, K, NB, NS, FERRO);
-  static constexpr int E = AL.E, NE = AL.NE, NL = AL.NL, NTM = AL.NTM;
-  static constexpr int RF = (E + 63) / 64, RE = (NE + 63) / 64, RL = (NL + 63) / 64;
-  static constexpr int RF1 = RF > 0 ? RF : 1, RL1 = RL > 0 ? RL : 1;
-  static constexpr int EP = E / 2, RP = (EP + 63) / 64, RP1 = RP > 0 ? RP : 1;  // Ferro element pairs (k, k+1)
-  static_assert(K % 2 == 0, "Ferro elements are walked in (k, k+1) pairs");
-  static constexpr int LPI = pow2_floor(64 / IN);  // lanes per input in the d/dx segmented sum
-  // cb row pitch: NTM rounded up to LPI mod 32, so the LPI-lane groups of one half-wave read
-  // distinct LDS banks in reduce_gin (a pitch of 32 put all ten inputs of layer 1 on banks 0-3)
-  // (extra padding of 4 / 12 / 16 floats measured within 1 %: the pitch is not a lever)
-  static constexpr int NTMP = LPI >= 32 ? NTM : NTM + ((LPI - NTM % 32) % 32 + 32) % 32;
-  static_assert(IN <= 64 && OUT <= 64, "layer widths up to 64");
-  static_assert(NS >= 1, "grid too small for cubic splines");
-};
-
-// Per-block LDS tables of the whole field.  Per-INPUT tables are laid out over the combined input
-// index t in [0, W): t < D are layer-0 inputs, t >= D layer-1 inputs (same knot count), so the
-// feature phase is one code path for both layers.
-template <int W, int NG, int NB>
-struct BInTab {
-  static constexpr int NI = NG - 1;
-  // basis B_{m-3+r} on interval m as a cubic in u: [t][m][r] (power basis); one float4 of
-  // padding per input so that lanes gathering different inputs' rows spread over the LDS banks
-  static constexpr int BPS = NI * 4 + 1;
-  float4 bp[W * BPS];
-  __device__ static int bpi(int t, int m) { return t * BPS + m * 4; }
-  float knots[W * NG];
-  float rh[W * NI];       // 1/(g[m+1] - g[m])
-  __attribute__((aligned(8))) float lg[NB > 0 ? 2 * W * NB : 1];  // (-a log2e, a b log2e) per (t, j)
-
-  __device__ void stage(const float* __restrict__ plan, const LayerPlan& P0, const LayerPlan& P1, int D, int tid,
-                        int nt) {
-    for (int q = tid; q < W * NG; q += nt) {
-      const int t = q / NG, j = q % NG;
-      knots[q] = t < D ? plan[P0.knots + t * NG + j] : plan[P1.knots + (t - D) * NG + j];
-    }
-    for (int q = tid; q < W * NI; q += nt) {
-      const int t = q / NI, m = q % NI;
-      rh[q] = t < D ? plan[P0.rh + t * NI + m] : plan[P1.rh + (t - D) * NI + m];
-    }
-    for (int q = tid; q < 2 * W * NB; q += nt)
-      lg[q] = q < 2 * D * NB ? plan[P0.lg + q] : plan[P1.lg + (q - 2 * D * NB)];
-    // basis polynomials: Cox-de Boor (efficientkan.py:117-131) restricted to interval m, in
-    // fp64 at u = 0, 1/3, 2/3, 1, converted to the power basis (exact for cubics)
-    for (int q = tid; q < W * NI; q += nt) {
-      const int t = q / NI, m = q % NI;
-      const float* g = t < D ? plan + P0.knots + t * NG : plan + P1.knots + (t - D) * NG;
-      const double h = (double)g[m + 1] - g[m];
-      double v[4][kSO + 2];
-      for (int s = 0; s < 4; ++s) {
-        const double x = g[m] + h * (s / 3.0);
-        double* N = v[s];
-        for (int r = 0; r < kSO + 2; ++r) N[r] = 0.0;
-        N[kSO] = 1.0;
-        for (int k = 1; k <= kSO; ++k) {
-          double M[kSO + 2];
-          for (int r = 0; r < kSO + 2; ++r) M[r] = 0.0;
-          for (int r = kSO - k; r <= kSO; ++r) {
-            const int j = m - kSO + r;
-            if (j >= 0 && j <= NG - 2 - k) {
-              const double left = (x - g[j]) / ((double)g[j + k] - g[j]) * N[r];
-              const double right = ((double)g[j + k + 1] - x) / ((double)g[j + k + 1] - g[j + 1]) * N[r + 1];
-              M[r] = left + right;
-            }
-          }
-          for (int r = 0; r < kSO + 2; ++r) N[r] = M[r];
-        }
-      }
-      for (int r = 0; r <= kSO; ++r) {
-        const double a0 = v[0][r], a1 = v[1][r], a2 = v[2][r], a3 = v[3][r];
-        bp[bpi(t, m) + r] = make_float4((float)a0, (float)((-11.0 * a0 + 18.0 * a1 - 9.0 * a2 + 2.0 * a3) / 2.0),
-                                    (float)(9.0 * (2.0 * a0 - 5.0 * a1 + 4.0 * a2 - a3) / 2.0),
-                                    (float)(9.0 * (-a0 + 3.0 * a1 - 3.0 * a2 + a3) / 2.0));
-      }
-    }
-  }
-};
-
-template <class L>
-struct BTab {  // per-block LDS copy of one layer's edge tables
-  // spline edge (o, i) as a cubic in u per interval (NI + 1 rows: the last is the zero row), rows
-  // of one edge padded to SPS float4s (lanes gather different edges: spread over the banks)
-  static constexpr int SPS = L::NI + 2;
-  float4 sp[L::OUT * L::IN * SPS];
-  float kw[L::OUT * L::IN * L::NFL];        // SiLU weight, 2 * scaled logistic weights
-  float pa[L::NL > 0 ? L::NL : 1], pb[L::NL > 0 ? L::NL : 1];
-  // Ferro element pair p = elements (2p, 2p + 1) = (i, o, k..k+1):
-  //   fpa = (Ec, Ec', 2 log2e k, 2 log2e k'),  fpb = (coef Ps k, coef' Ps' k', gs log2e Ec, gs log2e Ec')
-  float4 fpa[L::EP > 0 ? L::EP : 1], fpb[L::EP > 0 ? L::EP : 1];
-
-  __device__ void stage(const fetode_kanlinear_t& kl, const fetode_ferro_t& fl, const float* __restrict__ plan,
-                        const LayerPlan& P, int tid, int nt) {
-    const float gl = L::FERRO ? P.gsl2e : 0.f, k2 = 2.0f * FETODE_LOG2E;
-    for (int p = tid; p < L::EP; p += nt) {
-      const int e = 2 * p;
-      fpa[p] = make_float4(fl.Ec[e], fl.Ec[e + 1], k2 * fl.k[e], k2 * fl.k[e + 1]);
-      fpb[p] = make_float4((fl.coef[e] * fl.Ps[e]) * fl.k[e], (fl.coef[e + 1] * fl.Ps[e + 1]) * fl.k[e + 1],
-                           gl * fl.Ec[e], gl * fl.Ec[e + 1]);
-    }
-    const float4* src = reinterpret_cast<const float4*>(plan + P.sp);
-    for (int q = tid; q < L::OUT * L::IN * (L::NI + 1); q += nt) sp[q / (L::NI + 1) * SPS + q % (L::NI + 1)] = src[q];
-    for (int q = tid; q < L::OUT * L::IN * L::NFL; q += nt) kw[q] = plan[P.kw + q];
-    for (int q = tid; q < L::NL; q += nt) {
-      pa[q] = kl.logistic_a[q];
-      pb[q] = kl.logistic_b[q];
-    }
-  }
-};
-
-template <int W, int NS, int NB, bool WIN = false>
-struct BFeat {  // per-wave LDS features of both layers' inputs, combined index t
-  // dense B-spline row of input t at bd[t * BDP + BD0 + c].  WIN: the interval's four bases are
-  // written at c = m - 3 .. m into a filled row, so the rows carry kSO guard floats on either side
-  // (BD0 keeps the data 16-byte aligned; BDP = 4 mod 8 spreads the inputs over the banks); without
-  // WIN (the adjoint-only sweep, whose 4 waves per SIMD leave no LDS for guards) the row is dense
-  static constexpr bool WINDOW = WIN;
-  static constexpr int BD0 = WIN ? 4 : 0;
-  static constexpr int BDP0 = (BD0 + NS + kSO + 3) / 4 * 4;
-  static constexpr int BDP = !WIN ? NS : BDP0 % 8 == 0 ? BDP0 + 4 : BDP0;
-  __device__ static int bdi(int t, int c) { return t * BDP + BD0 + c; }
-  float4 g4[W];  // Ferro per-input terms: x, gate up, wo = wc (1 - up), -ln2 wo
-  float x[W], pv[W], silu[W], dsilu[W], u[W], rhm[W];  // rhm: 1 / (knot step) of x's interval
-  int m[W];
-  __attribute__((aligned(16))) float bd[W * BDP];
-  float sg[NB > 0 ? W * NB : 1];
-};
-
-template <class L>
-struct BReg {  // per-lane register slice of one layer: its gradient sums
-  f2 A[L::RP1], C[L::RP1], Ev[L::RP1];  // element pairs
-  float G;
-  float base[L::RE], spl[L::RE][L::NS];
-  float lw[L::RL1][L::OUT], la[L::RL1], lb[L::RL1];
-
-  __device__ void zero() {
-#pragma unroll
-    for (int r = 0; r < L::RP1; ++r) A[r] = C[r] = Ev[r] = splat(0.f);
-    G = 0.f;
-#pragma unroll
-    for (int r = 0; r < L::RE; ++r) {
-      base[r] = 0.f;
-#pragma unroll
-      for (int c = 0; c < L::NS; ++c) spl[r][c] = 0.f;
-    }
-#pragma unroll
-    for (int r = 0; r < L::RL1; ++r) {
-      la[r] = lb[r] = 0.f;
-#pragma unroll
-      for (int o = 0; o < L::OUT; ++o) lw[r][o] = 0.f;
-    }
-  }
-
-  // TPW > 1: job sets that fit in 64 / TPW lanes ran once per trajectory on lanes tt * LPT + job
-  // (layer_jobs), so their sums are combined here, trajectories in order
-  template <int TPW>
-  __device__ void store(float* __restrict__ part, int lane) {
-    constexpr AccLayout AL = L::AL;
-    constexpr int LPT = 64 / TPW;
-    auto comb = [&](float v) {
-      float t = v;
-#pragma unroll
-      for (int k = 1; k < TPW; ++k) t += __shfl(v, lane + k * LPT);
-      return t;
-    };
-    if constexpr (TPW > 1 && L::NE <= LPT) {
-      base[0] = comb(base[0]);
-#pragma unroll
-      for (int c = 0; c < L::NS; ++c) spl[0][c] = comb(spl[0][c]);
-    }
-    if constexpr (TPW > 1 && L::NL <= LPT) {
-#pragma unroll
-      for (int o = 0; o < L::OUT; ++o) lw[0][o] = comb(lw[0][o]);
-      la[0] = comb(la[0]);
-      lb[0] = comb(lb[0]);
-    }
-#pragma unroll
-    for (int r = 0; r < L::RP; ++r) {
-      const int e = 2 * (lane + 64 * r);
-      if (e < L::E) {
-        part[AL.oA + e] = A[r].x;
-        part[AL.oA + e + 1] = A[r].y;
-        part[AL.oC + e] = C[r].x;
-        part[AL.oC + e + 1] = C[r].y;
-        part[AL.oE + e] = Ev[r].x;
-        part[AL.oE + e + 1] = Ev[r].y;
-      }
-    }
-    if (L::FERRO && lane < L::OUT) part[AL.oG + lane] = G;
-#pragma unroll
-    for (int r = 0; r < L::RE; ++r) {
-      const int q = lane + 64 * r;
-      if (q < L::NE) {
-        part[AL.oBase + q] = base[r];
-#pragma unroll
-        for (int c = 0; c < L::NS; ++c) part[AL.oSpl + q * L::NS + c] = spl[r][c];
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < L::RL; ++r) {
-      const int q = lane + 64 * r;
-      if (q < L::NL) {
-#pragma unroll
-        for (int o = 0; o < L::OUT; ++o) part[AL.oLw + o * L::NL + q] = lw[r][o];
-        part[AL.oLa + q] = la[r];
-        part[AL.oLb + q] = lb[r];
-      }
-    }
-  }
-};
-
-__device__ __forceinline__ float sigm_l2(float zl) { return rcp(1.0f + ex2(zl)); }  // 1/(1+2^zl)
-
-// The lanes of one wave exchange data only through that wave's private LDS region.  DS
-// instructions of one wave execute in issue order, so a compiler barrier plus a wait for the
-// wave's own LDS traffic replaces the workgroup barrier (global loads in flight — the tape
-// prefetch — are not waited for).
-__device__ __forceinline__ void wsync() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-
-// sum over aligned groups of G lanes (G a power of two <= 32), result on every lane of the group
-template <int G>
-__device__ __forceinline__ float group_sum(float v) {
-  if constexpr (G >= 2) v += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, false));
-  if constexpr (G >= 4) v += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, false));
-  if constexpr (G == 8) v += __shfl_xor(v, 4);
-  if constexpr (G >= 16) {  // row_ror 4 then 8: every lane of the 16-lane row holds the row sum
-    v += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0x124, 0xF, 0xF, false));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0x128, 0xF, 0xF, false));
-  }
-  if constexpr (G >= 32) v += __shfl_xor(v, 16);
-  static_assert(G <= 32, "group up to 32 lanes");
-  return v;
-}
-
-// features of combined input t (one lane): SiLU, SiLU', knot interval, u, dense bases, gate
-template <int W, int NG, int NB, bool WIN>
-__device__ __forceinline__ void feat_input(BFeat<W, NG - 1 - kSO, NB, WIN>& F, const BInTab<W, NG, NB>& Tb, int t,
-                                           float gsl2e, float wc, float gs, int z) {
-  constexpr int NI = NG - 1, NS = NG - 1 - kSO;
-  const float x = F.x[t];
-  const float sx = sigm_l2(-x * FETODE_LOG2E);
-  F.silu[t] = x * sx;
-  F.dsilu[t] = sx * ffma(x, 1.0f - sx, 1.0f);
-  const float* g = &Tb.knots[t * NG + z];
-  int m = -1;
-  if constexpr (NG % 4 == 0) {  // the row as float4s: every knot read issued at once
-    const float4* g4 = reinterpret_cast<const float4*>(g);
-#pragma unroll
-    for (int j = 0; j < NG / 4; ++j) {
-      const float4 v = g4[j];
-      m += ((x >= v.x) ? 1 : 0) + ((x >= v.y) ? 1 : 0) + ((x >= v.z) ? 1 : 0) + ((x >= v.w) ? 1 : 0);
-    }
-  } else {
-#pragma unroll
-    for (int j = 0; j < NG; ++j) m += (x >= g[j]) ? 1 : 0;
-  }
-  const bool fin = __builtin_isfinite(x);
-  const bool in = fin && m >= 0 && m < NI;
-  const int mc = in ? m : 0;
-  const float rhm = Tb.rh[t * NI + mc + z];
-  const float u = in ? (x - g[mc]) * rhm : (fin ? 0.f : __builtin_nanf(""));
-  F.rhm[t] = rhm;
-  F.m[t] = in ? m : NI;
-  F.u[t] = u;
-  using FB = BFeat<W, NS, NB, WIN>;
-  float* bd = &F.bd[FB::bdi(t, 0)];
-  // non-finite x: NaN bases like the reference's (x - g)/d * 0; outside the grid: all zero
-  const float fill = fin ? 0.f : __builtin_nanf("");
-  // the interval's four basis cubics, all reads issued before any use
-  const float4* bp = &Tb.bp[Tb.bpi(t, mc) + z];
-  float4 p[kSO + 1];
-#pragma unroll
-  for (int r = 0; r <= kSO; ++r) p[r] = bp[r];
-  float v[kSO + 1];
-#pragma unroll
-  for (int r = 0; r <= kSO; ++r) v[r] = ffma(ffma(ffma(p[r].w, u, p[r].z), u, p[r].y), u, p[r].x);
-  // dense row through the LDS window: the row filled, then bases m - 3 .. m written over it (one
-  // wave's LDS writes land in issue order; c outside [0, NS) falls in the guards, and off the grid
-  // mc = 0 puts the fill over c = 0 again)
-  if constexpr (WIN) {
-    if constexpr (NS % 4 == 0) {
-#pragma unroll
-      for (int c = 0; c < NS; c += 4) *reinterpret_cast<float4*>(&bd[c]) = make_float4(fill, fill, fill, fill);
-    } else {
-#pragma unroll
-      for (int c = 0; c < NS; ++c) bd[c] = fill;
-    }
-#pragma unroll
-    for (int r = 0; r <= kSO; ++r) bd[mc - kSO + r] = in ? v[r] : fill;
-  } else {  // formed in registers (select chains) and written once
-#pragma unroll
-    for (int c = 0; c < NS; ++c) {
-      float b = fill;
-#pragma unroll
-      for (int r = 0; r <= kSO; ++r) b = (in && c == mc - kSO + r) ? v[r] : b;
-      bd[c] = b;
-    }
-  }
-  const float up = sigm_l2(-gsl2e * (x - F.pv[t]));
-  const float wo = wc * (1.0f - up);
-  F.g4[t] = make_float4(x, up, wo, -0.69314718f * wo);
-}
-
-// the VJP jobs of one layer (inputs at combined offset TB) for one evaluation of each of the
-// wave's TPW trajectories (Fs[tt], gouts + tt * GS, cbs + tt * CBS): gradient sums into R (the
-// lane's job slots, summed over the trajectories in order), d out/d x contributions into
-// cb[i * NTMP + t]
-template <class L, int TB, bool ACC, int TPW, int GS, int CBS, class FT>
-__device__ __forceinline__ void layer_jobs(const FT* Fs, const float* __restrict__ gouts, const BTab<L>& Tb,
-                                           const float* __restrict__ rhs, BReg<L>& R, float* __restrict__ cbs,
-                                           float gsl2e, float wc, float gs, int lane, int z) {
-  if constexpr (L::FERRO && !(FETODE_EXP_SKIP & 1)) {
-    // element pairs (k, k+1) of one (i, o) on packed-fp32 ops; with wo = wc (1 - up), c' = c (1 - c):
-    //   c = sigmoid(gs(-x - Ec)), m = 1 + wo c, sh = x + Ec m, th = tanh(k sh), q = g (1 - th^2)
-    //   A += g th, C += q sh, E += q (m + Ec dm/dEc) with Ec dm/dEc = (-gs Ec) wo c'
-    //   d out/d x = q coef Ps k (1 + Ec dm/dx) with dm/dx = -gs wo (up c + c');
-    //   (-gs Ec) wo is formed once per pair as (gs log2e Ec)(-ln2 wo)
-#pragma unroll
-    for (int tt = 0; tt < TPW; ++tt)  // trajectories in turn, each one's rounds interleaved
-#pragma unroll
-    for (int r = 0; r < L::RP; ++r) {
-      const int p = lane + 64 * r;
-      if (p < L::EP) {
-        const FT& F = Fs[tt];
-        const float* gout = gouts + tt * GS;
-        float* cb = cbs + tt * CBS;
-        const int e = 2 * p, i = e / (L::OUT * L::K), ok_ = e % (L::OUT * L::K);
-        const int o = ok_ / L::K;
-        const float4 g = F.g4[TB + i];
-        const float go = gout[o];
-        const float4 fa = Tb.fpa[p + z], fb = Tb.fpb[p + z];
-        const f2 Ec = f2{fa.x, fa.y}, k2 = f2{fa.z, fa.w}, cPk = f2{fb.x, fb.y}, Eg2 = f2{fb.z, fb.w};
-        const f2 x = splat(g.x), wo = splat(g.z), gv = splat(go);
-        const f2 cn = rcpx2(ex2x2(pfma(x, splat(gsl2e), Eg2)) + splat(1.0f));  // sigmoid(gs(-x - Ec))
-        const f2 mm = pfma(wo, cn, splat(1.0f));                           // branch_mom, branch_sign = 1
-        const f2 sh = pfma(Ec, mm, x);                                     // shifted_x
-        const f2 th = pfma(splat(-2.0f), rcpx2(ex2x2(k2 * sh) + splat(1.0f)), splat(1.0f));  // tanh(k sh)
-        const f2 q = gv * pfma(-th, th, splat(1.0f));
-        const f2 dcn = pfma(-cn, cn, cn);
-        const f2 ew = Eg2 * splat(g.w);  // (-gs Ec) wo
-        if constexpr (ACC) {
-          R.A[r] = pfma(gv, th, R.A[r]);
-          R.C[r] = pfma(q, sh, R.C[r]);
-          R.Ev[r] = pfma(q, pfma(ew, dcn, mm), R.Ev[r]);
-        }
-        // Ec dm/dx = ew (up c + c')
-        *reinterpret_cast<f2*>(&cb[i * L::NTMP + ok_]) = (q * cPk) * pfma(ew, pfma(splat(g.y), cn, dcn), splat(1.0f));
-      }
-    }
-    if constexpr (ACC)
-      if (lane < L::OUT)
-#pragma unroll
-        for (int tt = 0; tt < TPW; ++tt) R.G += gouts[tt * GS + lane];
-  }
-  // KAN edges (and below, logistic pairs): when one trajectory's jobs fit in 64 / TPW lanes, every
-  // trajectory's jobs run in ONE round (lane = tt * 64 / TPW + job); the lane sums of one job are
-  // combined across trajectories once, at store
-  auto edge = [&](int tt, int q, int r) __attribute__((always_inline)) {
-    {
-      const FT& F = Fs[tt];
-      float* cb = cbs + tt * CBS;
-      const int o = q / L::IN, i = q % L::IN;
-      const float go = gouts[tt * GS + o];
-      if constexpr (ACC) {
-        R.base[r] = ffma(go, F.silu[TB + i], R.base[r]);
-#pragma unroll
-        for (int c = 0; c < L::NS; ++c) R.spl[r][c] = ffma(go, F.bd[FT::bdi(TB + i, c)], R.spl[r][c]);
-      }
-      const int m = F.m[TB + i];
-      const float u = F.u[TB + i];
-      // (o, i, interval), q = o*IN + i; off the grid m = NI reads the zero row, so dsdx is 0 there
-      // (u = 0) and NaN for non-finite inputs (u = NaN): the reference's NaN bases, branch-free
-      const float4 cf = Tb.sp[q * BTab<L>::SPS + m + z];
-      const float dsdx = ffma(u, ffma(3.0f * u, cf.w, 2.0f * cf.z), cf.y) * F.rhm[TB + i];
-      const float wb = Tb.kw[o * (L::IN * L::NFL) + i * L::NFL + z];
-      cb[i * L::NTMP + L::OUT * L::K + o] = go * ffma(wb, F.dsilu[TB + i], dsdx);
-    }
-  };
-  constexpr int LPT = 64 / TPW;
-  if constexpr (FETODE_EXP_SKIP & 2) {
-  } else if constexpr (L::NE <= LPT) {
-    if (lane % LPT < L::NE) edge(lane / LPT, lane % LPT, 0);
-  } else {
-#pragma unroll 1
-    for (int tt = 0; tt < TPW; ++tt)
-#pragma unroll
-    for (int r = 0; r < L::RE; ++r)
-      if (lane + 64 * r < L::NE) edge(tt, lane + 64 * r, r);
-  }
-  auto logi = [&](int tt, int q, int r) __attribute__((always_inline)) {
-    {
-      const FT& F = Fs[tt];
-      const float* gout = gouts + tt * GS;
-      float* cb = cbs + tt * CBS;
-      const int i = q / L::NB, j = q % L::NB;
-      const float s = F.sg[TB * L::NB + q], ds = s * (1.0f - s), x = F.x[TB + i];
-      float S = 0.f;
-#pragma unroll
-      for (int o = 0; o < L::OUT; ++o) {
-        const float go = gout[o];
-        S = ffma(go, Tb.kw[o * (L::IN * L::NFL) + i * L::NFL + 1 + j + z], S);
-        if constexpr (ACC) R.lw[r][o] = ffma(go, s, R.lw[r][o]);
-      }
-      const float T = S * ds;  // kw holds 2 * scaled logistic weight: d(2 sigmoid) folded in
-      const float pa = Tb.pa[q + z];
-      if constexpr (ACC) {
-        R.la[r] = ffma(T, x - Tb.pb[q + z], R.la[r]);
-        R.lb[r] = ffma(-T, pa, R.lb[r]);
-      }
-      cb[i * L::NTMP + L::OUT * L::K + L::OUT + j] = T * pa;
-    }
-  };
-  if constexpr (FETODE_EXP_SKIP & 4) {
-  } else if constexpr (L::NL <= LPT) {
-    if (lane % LPT < L::NL) logi(lane / LPT, lane % LPT, 0);
-  } else {
-#pragma unroll 1
-    for (int tt = 0; tt < TPW; ++tt)
-#pragma unroll
-    for (int r = 0; r < L::RL; ++r)
-      if (lane + 64 * r < L::NL) logi(tt, lane + 64 * r, r);
-  }
-}
-
-// gin[i] = sum_t cb[i * NTMP + t], fixed order: LPI lanes per input, each summing a contiguous
-// run of float4 chunks, then a DPP tree; with TPW trajectories per wave each takes 64 / TPW lanes
-// (cbs + tt * CBS -> gins + tt * GS)
-template <class L, int TPW, int GS, int CBS>
-__device__ __forceinline__ void reduce_gin(const float* __restrict__ cbs, float* gins, int lane) {
-  if constexpr (FETODE_EXP_SKIP & 16) return;
-  constexpr int HALF = 64 / TPW;
-  constexpr int LPI0 = pow2_floor(HALF / L::IN);
-  constexpr int LPI = LPI0 > 32 ? 32 : (L::LPI < LPI0 ? L::LPI : LPI0);
-  constexpr int C4 = (L::NTM + 4 * LPI - 1) / (4 * LPI);  // float4 chunks per lane
-  static_assert(L::NTM % 4 == 0 && L::NTMP % 4 == 0 && CBS % 4 == 0, "float4 rows of the cb table");
-  const int tt = lane / HALF, sl = lane % HALF;
-  const int i = sl / LPI, sub = sl % LPI;
-  const float4* cb = reinterpret_cast<const float4*>(cbs + tt * CBS + i * L::NTMP);
-  float s = 0.f;
-  if (i < L::IN) {
-#pragma unroll
-    for (int k = 0; k < C4; ++k) {
-      const int c = sub * C4 + k;
-      if (4 * c < L::NTM) {
-        const float4 v = cb[c];
-        s += (v.x + v.y) + (v.z + v.w);
-      }
-    }
-  }
-  s = group_sum<LPI>(s);
-  if (i < L::IN && sub == 0) gins[tt * GS + i] = s;
-}
-
-struct BwdArgs {
-  const float* plan;
-  LayerPlan P0, P1;
-  fetode_kanlinear_t k0, k1;
-  fetode_ferro_t f0, f1;
-  int32_t method;
-  int64_t B;
-  const float* step_coef;
-  int32_t n_steps;
-  const int32_t* out_step;
-  const int32_t* out_mode;
-  const float* out_slope;
-  int32_t T;
-  const float* gsol;    // (T, B, D)
-  const float* tape;    // (n_evals, B, D + H)
-  const float* state0;  // hysteresis state before the solve (include/fetode.h layout)
-  uint32_t init_mask;
-  float* gy0;           // (B, D) or null
-  float* part;          // (rows, nacc)
-  int32_t nacc;
-  float* gadj;          // (n_evals, B, D + H): d loss / d k (D) and d loss / d h (H) per evaluation
-};
-
-// stage-combine coefficients of one step in the forward's fp32 arithmetic (odeint.py
-// _combine_coefs): y1 = y + sum_j bc[j] k_j,  X_st = y + sum_{j<st} ac[st][j] k_j
-__device__ __forceinline__ void step_coefs(int method, float dt, float hh, float h6, float bc[4], float ac[4][3]) {
-  const float third = 1.0f / 3.0f;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    bc[i] = 0.f;
-#pragma unroll
-    for (int j = 0; j < 3; ++j) ac[i][j] = 0.f;
-  }
-  if (method == FETODE_RK4) {  // rk_common.rk4_alt_step_func (3/8 rule)
-    bc[0] = dt * 0.125f;
-    bc[1] = 3.0f * dt * 0.125f;
-    bc[2] = 3.0f * dt * 0.125f;
-    bc[3] = dt * 0.125f;
-    ac[1][0] = dt * third;
-    ac[2][0] = -dt * third;
-    ac[2][1] = dt;
-    ac[3][0] = dt;
-    ac[3][1] = -dt;
-    ac[3][2] = dt;
-  } else if (method == FETODE_RK4_CLASSIC) {  // train_kan_fet_ett.py:72-75
-    bc[0] = h6;
-    bc[1] = 2.0f * h6;
-    bc[2] = 2.0f * h6;
-    bc[3] = h6;
-    ac[1][0] = hh;
-    ac[2][1] = hh;
-    ac[3][2] = dt;
-  } else if (method == FETODE_MIDPOINT) {
-    bc[1] = dt;
-    ac[1][0] = hh;
-  } else {
-    bc[0] = dt;
-  }
-}
-
-constexpr int kTPB = 4;  // trajectories (waves) per workgroup, sharing one copy of the tables
-#ifndef FETODE_BWD_WAVES
-#define FETODE_BWD_WAVES 2  // minimum waves per SIMD the register allocation must allow
-#endif
+#include "fetode_bwd_dev.h"
 
 // ACC = true: the whole reverse sweep in one kernel — adjoints and the parameter-gradient sums (in
 // VGPRs, one partial row per wave).  ACC = false: the adjoint sweep only (no sums: 114 VGPRs, four
@@ -840,491 +272,11 @@ __global__ __launch_bounds__(64 * kTPB) __attribute__((amdgpu_waves_per_eu(ACC ?
 //   carry     y's adjoint and f0's (= k_1's) to the attempt that produced them
 // After attempt 0: _select_initial_step's adjoint (one more grid sum, through the probe).
 // =============================================================================================
-struct DopriBwdArgs {
-  BwdArgs b;            // plan, layers, B, T, gsol, tape ((n_ev, B, 2 D + H): inputs, output), state0, ...
-  const double* att;    // (n_att, 4): t0, dt, error ratio, accepted
-  int32_t n_att, n_ev, base;  // base: evaluation index of attempt 0's stage 2 (1 with first_step, else 2)
-  const double* t;      // (T) output times, fp64
-  const double* init_rec;  // {d0, d1, d2, h0, h1}
-  float beta[6][6], cerr[7], cmid[7];
-  float rtol, atol;
-  double safety, ifactor, dfactor, min_step, max_step, n_el;
-  DopriParams gp;       // the grid-sum words and leaf layout (single device)
-  int32_t* status;      // 0, or 4 when a grid sum timed out
-};
-
-// a wave-uniform value computed on the VALU (or read from LDS) into SGPRs: it stays live across
-// the evaluations' VJPs without holding VGPRs
-__device__ __forceinline__ float unif(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(unsigned, v)));
-}
-__device__ __forceinline__ double uni(double v) {
-  const unsigned long long u = __double_as_longlong(v);
-  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)u), hi = __builtin_amdgcn_readfirstlane((unsigned)(u >> 32));
-  return __longlong_as_double(((unsigned long long)hi << 32) | lo);
-}
 
 template <int D, int H, int K, int NB, int NG, bool FERRO, int TPW>
 __global__ __launch_bounds__(64 * kTPB) __attribute__((amdgpu_waves_per_eu(FETODE_BWD_WAVES))) void dopri_bwd_kernel(DopriBwdArgs da) {
-  const BwdArgs& a = da.b;
-  using L0 = BL<D, H, K, NB, NG, FERRO>;
-  using L1 = BL<H, D, K, NB, NG, FERRO>;
-  constexpr int W = D + H, NS = NG - 1 - kSO, HALF = 64 / TPW;
-  constexpr int CB = L0::IN * L0::NTMP > L1::IN * L1::NTMP ? L0::IN * L0::NTMP : L1::IN * L1::NTMP;
-  constexpr bool PF = FERRO && 2 * W <= HALF;
-  constexpr int FH = PF ? HALF / 2 : HALF, NBUF = PF ? 2 : 1;
-  static_assert(W <= FH && (TPW == 1 || TPW == 2 || TPW == 4), "one lane per input of each trajectory and evaluation");
-  __shared__ BInTab<W, NG, NB> TI;
-  __shared__ BTab<L0> T0;
-  __shared__ BTab<L1> T1;
-  using FB = BFeat<W, NS, NB, PF>;
-  __shared__ FB sF[kTPB][NBUF][TPW];
-  __shared__ __attribute__((aligned(16))) float s_cb[kTPB][TPW][CB];
-  __shared__ float s_g1[kTPB][TPW][D], s_g0[kTPB][TPW][H], s_gx[kTPB][TPW][D];
-  __shared__ float s_k[kTPB][TPW][8][D], s_kb[kTPB][TPW][8][D];  // k_1..k_7 and their adjoints
-  __shared__ double s_red[kTPB][2], s_res[2];
-  __shared__ int s_ab;
-  // the element lanes' carried adjoints, kept in LDS across the VJPs (register pressure)
-  struct ElSt {
-    double pd, pt;          // this attempt's d/d dt and d/d t0 terms of the outputs (+ d/d dt32 at the end)
-    float yb0, yb1, dtb32;  // adjoints of the attempt's y, y1, dt32
-    float ybc, fbc;         // carried: adjoints of the current y and f0
-    float scb, f0bp;        // initial step: adjoint of scale, the probe's term of f0's adjoint
-  };
-  __shared__ ElSt s_el[kTPB][TPW][D];
-  // the tableau in LDS: kernel-argument reads with constant indices would be hoisted into ~50
-  // SGPRs for the whole loop (the VJP needs the SGPR file)
-  __shared__ float s_beta[6][6], s_cerr[8], s_cmid[8];
-  // the wave-uniform control scalars, per wave in LDS: they are touched once per attempt and would
-  // otherwise hold registers across every VJP (adjoints of the next dt and of t1s, ...)
-  struct WSc {
-    double dtbar, tbar, dtb_base, h0b, d0b, d1b;
-    float dt32, h0f;
-    int jj, acc;
-  };
-  __shared__ WSc s_sc[kTPB];
-  // the arguments the per-attempt code reads, in LDS: read from the kernel arguments inside the
-  // loop they would be hoisted into SGPRs (and spilled) for the whole sweep
-  struct RareArgs {
-    const double* att;
-    const double* t;
-    const float* gsol;
-    float* gy0;
-    const double* init_rec;
-    int64_t B;
-    int base, n_att;
-    float rtol, atol;
-    double n_el, safety, ifactor, dfactor, min_step, max_step;
-  };
-  __shared__ RareArgs s_ra;
-
-  const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int tt = lane / HALF, sl = lane % HALF;
-  const int fb = sl / FH, fsl = sl % FH;
-  TI.stage(a.plan, a.P0, a.P1, D, threadIdx.x, 64 * kTPB);
-  T0.stage(a.k0, a.f0, a.plan, a.P0, threadIdx.x, 64 * kTPB);
-  T1.stage(a.k1, a.f1, a.plan, a.P1, threadIdx.x, 64 * kTPB);
-  BReg<L0> R0;
-  BReg<L1> R1;
-  R0.zero();
-  R1.zero();
-  if (threadIdx.x == 0) {
-    s_ab = 0;
-    s_ra = RareArgs{da.att, da.t, a.gsol, a.gy0, da.init_rec, a.B, da.base, da.n_att, da.rtol, da.atol,
-                    da.n_el, da.safety, da.ifactor, da.dfactor, da.min_step, da.max_step};
-#pragma unroll
-    for (int q = 0; q < 36; ++q) s_beta[q / 6][q % 6] = da.beta[q / 6][q % 6];
-#pragma unroll
-    for (int q = 0; q < 7; ++q) {
-      s_cerr[q] = da.cerr[q];
-      s_cmid[q] = da.cmid[q];
-    }
-  }
-  __syncthreads();
-
-  float* cbs = &s_cb[wid][0][0];
-  float* g1s = &s_g1[wid][0][0];
-  float* g0s = &s_g0[wid][0][0];
-  float* gxs = &s_gx[wid][0][0];
-  float(&kk)[8][D] = s_k[wid][tt];
-  float(&kb)[8][D] = s_kb[wid][tt];
-  const float gs0 = (float)a.f0.gate_slope, gs1 = (float)a.f1.gate_slope;
-  const float gl0 = a.P0.gsl2e, gl1 = a.P1.gsl2e, wc0 = a.P0.wc, wc1 = a.P1.wc;
-  const float glane = fsl < D ? gl0 : gl1, wlane = fsl < D ? wc0 : wc1, slane = fsl < D ? gs0 : gs1;
-  constexpr int TW = 2 * D + H;  // tape row: layer-0 input, layer-1 input, output k
-  const int64_t tstride = a.B * TW;
-  const int n_ev = da.n_ev;
-  const int64_t b0 = ((int64_t)blockIdx.x * kTPB + wid) * TPW;
-  const int64_t b = b0 + tt;
-  const bool live = b < a.B;
-  const bool el = live && sl < D;  // this lane carries element (b, sl)
-  // per-lane offsets in 32 bits, row bases uniform (scalar base + vector offset addressing)
-  const int bi = live ? (int)b : 0;
-  auto tape_at = [&](int ev) -> float {
-    if (fsl >= W || !live) return 0.f;
-    if (ev >= 0) return (a.tape + (int64_t)ev * tstride)[bi * TW + fsl];
-    const float v = a.tape[bi * TW + fsl];
-    if (fsl < D) return (a.init_mask & 1u) ? v : (FERRO ? a.state0[bi * D + fsl] : 0.f);
-    return (a.init_mask & 2u) ? v : (FERRO ? (a.state0 + a.B * D)[bi * H + (fsl - D)] : 0.f);
-  };
-  auto tx = [&](int ev) -> float { return (a.tape + (int64_t)ev * tstride)[bi * TW + sl]; };      // layer input (el lanes)
-  auto tk = [&](int ev) -> float { return (a.tape + (int64_t)ev * tstride)[bi * TW + W + sl]; };  // output (el lanes)
-  float cur = tape_at(n_ev - 1 - fb), prv = tape_at(n_ev - 2 - fb);
-
-  // the VJP of evaluation ev: g1s (d loss / d k) -> gxs (d loss / d layer-0 input); sums into R0, R1
-  auto vjp = [&](int ev) {
-    int z = 0;
-    asm volatile("" : "+s"(z));
-    const bool fstep = !PF || ((n_ev - 1 - ev) & 1) == 0;
-    float nx1 = 0.f, nx2 = 0.f;
-    FB& FF = sF[wid][PF ? (ev - fb) & 1 : 0][tt];
-    if (fstep) {
-      if constexpr (PF) {
-        nx1 = tape_at(ev - fb - 2);
-        nx2 = tape_at(ev - fb - 3);
-      } else {
-        nx1 = prv;
-        nx2 = tape_at(ev - 2);
-      }
-      if (fsl < W) {
-        FF.x[fsl] = cur;
-        FF.pv[fsl] = prv;
-      }
-    }
-    wsync();
-    if (fstep) {
-      if (fsl < W) feat_input<W, NG, NB, PF>(FF, TI, fsl, glane, wlane, slane, z);
-      constexpr int NSG = TPW * W * NB, RSG = (NSG + 63) / 64;
-#pragma unroll
-      for (int pb = 0; pb < NBUF; ++pb) {
-        FB* Fp = sF[wid][pb];
-        float sa[RSG], sb[RSG], sx[RSG];
-#pragma unroll
-        for (int k = 0; k < RSG; ++k) {
-          const int q = lane + 64 * k, qc = q < NSG ? q : 0;
-          const int qt = qc / (W * NB), qq = qc % (W * NB);
-          const float2 ab = *reinterpret_cast<const float2*>(&TI.lg[2 * qq + z]);
-          sa[k] = ab.x;
-          sb[k] = ab.y;
-          sx[k] = Fp[qt].x[qq / NB];
-        }
-#pragma unroll
-        for (int k = 0; k < RSG; ++k) {
-          const int q = lane + 64 * k;
-          if (q < NSG) {
-            const int qt = q / (W * NB), qq = q % (W * NB);
-            Fp[qt].sg[qq] = sigm_l2(ffma(sa[k], sx[k], sb[k]));
-          }
-        }
-      }
-      wsync();
-      cur = nx1;
-      prv = nx2;
-    }
-    FB* Fs = sF[wid][PF ? ev & 1 : 0];
-    layer_jobs<L1, D, true, TPW, D, CB>(Fs, g1s, T1, TI.rh, R1, cbs, gl1, wc1, gs1, lane, z);
-    wsync();
-    reduce_gin<L1, TPW, H, CB>(cbs, g0s, lane);
-    wsync();
-    layer_jobs<L0, 0, true, TPW, H, CB>(Fs, g0s, T0, TI.rh, R0, cbs, gl0, wc0, gs0, lane, z);
-    wsync();
-    reduce_gin<L0, TPW, D, CB>(cbs, gxs, lane);
-    wsync();
-  };
-
-  // grid-wide fixed-order sum of two per-lane fp64 values (every workgroup gets the same result)
-  unsigned round = 0;
-  auto gsum = [&](double v0, double v1, double& s0, double& s1) {
-    v0 = xor_sum64(v0);
-    v1 = xor_sum64(v1);
-    if (lane == 0) {
-      s_red[wid][0] = v0;
-      s_red[wid][1] = v1;
-    }
-    __syncthreads();
-    if (wid == 0) {
-      double u0 = s_red[0][0], u1 = s_red[0][1];
-#pragma unroll
-      for (int w = 1; w < kTPB; ++w) {
-        u0 += s_red[w][0];
-        u1 += s_red[w][1];
-      }
-      double r0 = 0.0, r1 = 0.0;
-      const bool ab = grid_sum2(da.gp, round, u0, u1, r0, r1);
-      if (lane == 0) {
-        s_res[0] = r0;
-        s_res[1] = r1;
-        if (ab) s_ab = 1;
-      }
-    }
-    __syncthreads();
-    s0 = s_res[0];
-    s1 = s_res[1];
-  };
-
-  ElSt& E = s_el[wid][tt][sl < D ? sl : 0];  // written by lanes sl < D only
-  if (sl < D) {
-    E.ybc = E.fbc = 0.f;
-    E.scb = E.f0bp = 0.f;
-  }
-  // wave-uniform scalars (SGPRs): adjoints of the next dt and of t1s, this attempt's control terms
-  WSc& C = s_sc[wid];  // every lane writes the same values
-  C.dtbar = C.tbar = C.dtb_base = C.h0b = C.d0b = C.d1b = 0.0;
-  C.jj = a.T - 1;  // the last output not yet taken
-  C.dt32 = C.h0f = 0.f;
-  C.acc = 0;
-
-  for (int ev = n_ev - 1; ev >= 0; --ev) {
-    const bool in_att = ev >= s_ra.base;
-    const int n = in_att ? (ev - s_ra.base) / 6 : -1, s = in_att ? 2 + (ev - s_ra.base) % 6 : 0;
-    // ---------------- before the VJP: this evaluation's output adjoint ----------------
-    if (in_att && s == 7) {
-      const double t0 = s_ra.att[4 * n], dt = s_ra.att[4 * n + 1];
-      const float ratio = (float)s_ra.att[4 * n + 2];
-      C.acc = s_ra.att[4 * n + 3] != 0.0;
-      int m = n - 1;  // the attempt whose stage 7 produced this attempt's y and f0
-      while (m >= 0 && s_ra.att[4 * m + 3] == 0.0) --m;
-      const int fe = m >= 0 ? s_ra.base + 6 * m + 5 : 0;
-      const int e2 = s_ra.base + 6 * n;
-      C.dt32 = ((float)dt);
-      // control: dt_{n+1} = clamp(dt * min(ifactor, max(safety ratio^-1/5, dfac))) (rk_common.
-      // _optimal_step_size, fp64).  The factor the forward took is dt_{n+1} / dt_n from the attempt
-      // log, so no pow here: the middle term was taken unless the factor sits on a bound (or the
-      // clamp did), and its derivative is -factor / (5 ratio).  The last attempt's next dt feeds
-      // nothing (its adjoint is 0).
-      const double rr = (double)ratio;
-      double rbar = 0.0, dtbb = 0.0;
-      if (n + 1 < s_ra.n_att) {
-        const double dtn1 = s_ra.att[4 * (n + 1) + 1];
-        const bool clamped = (s_ra.min_step > 0.0 && dtn1 == s_ra.min_step) || dtn1 == s_ra.max_step;
-        if (!clamped) {
-          const double fac = dtn1 / dt;
-          dtbb = C.dtbar * fac;
-          if (rr > 0.0) {
-            const double dfac = rr < 1.0 ? 1.0 : s_ra.dfactor;
-            const bool bound = fabs(fac - s_ra.ifactor) <= 1e-12 * s_ra.ifactor || fabs(fac - dfac) <= 1e-12 * dfac;
-            if (!bound) rbar = C.dtbar * dt * (-0.2 * fac / rr);
-          }
-        }
-      }
-      C.dtb_base = dtbb;
-      double pd = 0.0, pt = 0.0;
-      float dtb32 = 0.f, yb0, yb1;
-      const float ybc = sl < D ? E.ybc : 0.f, fbc = sl < D ? E.fbc : 0.f;
-      float kv[8], kbv[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) kv[j] = kbv[j] = 0.f;
-      float y = 0.f, y1 = 0.f;
-      if (el) {
-        y = tx(fe);
-        kv[1] = tk(fe);
-#pragma unroll
-        for (int j = 2; j <= 7; ++j) kv[j] = tk(e2 + j - 2);
-        y1 = tx(e2 + 5);
-      }
-      // err and mid in the forward's op order (fetode_fused.hip DOPRI)
-      float err = kv[1] * (s_cerr[0] * C.dt32), midv = kv[1] * (s_cmid[0] * C.dt32);
-#pragma unroll
-      for (int j = 2; j <= 7; ++j) {
-        err = err + kv[j] * (s_cerr[j - 1] * C.dt32);
-        midv = midv + kv[j] * (s_cmid[j - 1] * C.dt32);
-      }
-      float midb = 0.f, fab;
-      if (C.acc) {
-        yb1 = ybc;
-        kbv[7] = fbc;
-        yb0 = 0.f;
-        fab = 0.f;
-        // interp._interp_fit (fetode_fused.hip's op order)
-        const float ym = y + midv, fa = kv[1], fbk = kv[7];
-        const float co1 = C.dt32 * fa;
-        const float co2 = ((C.dt32 * (fbk - 4.0f * fa) - 11.0f * y) - 5.0f * y1) + 16.0f * ym;
-        const float co3 = ((C.dt32 * (5.0f * fa - 3.0f * fbk) + 18.0f * y) + 14.0f * y1) - 32.0f * ym;
-        const float co4 = ((2.0f * C.dt32) * (fbk - fa) - 8.0f * (y1 + y)) + 16.0f * ym;
-        float c0 = 0.f, c1 = 0.f, c2 = 0.f, c3 = 0.f, c4 = 0.f;
-        const double t1 = t0 + dt, dlt = t1 - t0;
-        for (; C.jj >= 1 && s_ra.t[C.jj] > t0; --C.jj) {  // outputs in (t0, t1]: uniform over the grid
-          const float x = (float)((s_ra.t[C.jj] - t0) / dlt);
-          const float g = el ? (s_ra.gsol + (int64_t)C.jj * a.B * D)[bi * D + sl] : 0.f;
-          const float x2 = x * x, x3 = x2 * x;
-          c0 += g;
-          c1 += g * x;
-          c2 += g * x2;
-          c3 += g * x3;
-          c4 += g * (x3 * x);
-          const float dsdx = co1 + 2.0f * x * co2 + 3.0f * x2 * co3 + 4.0f * x3 * co4;
-          const double xb = (double)(g * dsdx);
-          pt += xb * (-1.0 / dlt);
-          pd += xb * (-(double)x / dlt);
-        }
-        yb0 += ((c0 - 11.0f * c2) + 18.0f * c3) - 8.0f * c4;
-        yb1 += (-5.0f * c2 + 14.0f * c3) - 8.0f * c4;
-        const float ymb = (16.0f * c2 - 32.0f * c3) + 16.0f * c4;
-        fab += C.dt32 * (((c1 - 4.0f * c2) + 5.0f * c3) - 2.0f * c4);
-        kbv[7] += C.dt32 * ((c2 - 3.0f * c3) + 2.0f * c4);
-        dtb32 += ((c1 * fa + c2 * (fbk - 4.0f * fa)) + c3 * (5.0f * fa - 3.0f * fbk)) + c4 * (2.0f * (fbk - fa));
-        yb0 += ymb;
-        midb = ymb;
-      } else {
-        yb0 = ybc;
-        fab = fbc;
-        yb1 = 0.f;
-      }
-      kbv[1] = fab;
-      // error ratio = rms(err / tol): d ratio / d qe = qe / (N ratio)
-      float errb = 0.f;
-      if (rbar != 0.0 && ratio > 0.f) {
-        const float tol = s_ra.atol + s_ra.rtol * fmaxf(fabsf(y), fabsf(y1));
-        const float qe = err / tol;
-        const float qb = (float)(rbar * (double)qe / (s_ra.n_el * rr));
-        errb = qb / tol;
-        const float tolb = -qb * qe / tol, ay = fabsf(y), ay1 = fabsf(y1);
-        const float sy = y > 0.f ? 1.f : (y < 0.f ? -1.f : 0.f), sy1 = y1 > 0.f ? 1.f : (y1 < 0.f ? -1.f : 0.f);
-        const float wy = ay > ay1 ? 1.f : (ay < ay1 ? 0.f : 0.5f);
-        yb0 += tolb * s_ra.rtol * wy * sy;
-        yb1 += tolb * s_ra.rtol * (1.f - wy) * sy1;
-      }
-      float se = 0.f, sm = 0.f;
-#pragma unroll
-      for (int j = 1; j <= 7; ++j) {
-        kbv[j] += errb * (s_cerr[j - 1] * C.dt32) + midb * (s_cmid[j - 1] * C.dt32);
-        se += s_cerr[j - 1] * kv[j];
-        sm += s_cmid[j - 1] * kv[j];
-      }
-      dtb32 += errb * se + midb * sm;
-      if (sl < D) {
-#pragma unroll
-        for (int j = 1; j <= 7; ++j) {
-          kk[j][sl] = kv[j];
-          kb[j][sl] = kbv[j];
-        }
-        E.pd = pd;
-        E.pt = pt;
-        E.yb0 = yb0;
-        E.yb1 = yb1;
-        E.dtb32 = dtb32;
-      }
-    } else if (!in_att && ev == 1) {
-      // _select_initial_step (dopri5.py select_initial_step, fp32): dt0 = min(100 h0, h1)
-      const float d0 = (float)s_ra.init_rec[0], d1 = (float)s_ra.init_rec[1], d2 = (float)s_ra.init_rec[2];
-      const float h0 = (float)s_ra.init_rec[3], h1 = (float)s_ra.init_rec[4];
-      C.h0f = (h0);
-      const double dtb = C.dtbar;
-      double h1b = 0.0;
-      C.h0b = 0.0;
-      const float a100 = 100.0f * h0, ah1 = fabsf(h1), sh1 = h1 < 0.f ? -1.f : 1.f;
-      if (a100 < ah1) C.h0b = 100.0 * dtb;
-      else if (ah1 < a100) h1b = dtb * sh1;
-      else {
-        C.h0b = 50.0 * dtb;
-        h1b = 0.5 * dtb * sh1;
-      }
-      double d2b = 0.0, d1b_ = 0.0;
-      if (d1 <= 1e-15f && d2 <= 1e-15f) {  // h1 = max(1e-6, h0 1e-3)
-        const float v = h0 * 1e-3f;
-        if (v > 1e-6f) C.h0b += 1e-3 * h1b;
-        else if (v == 1e-6f) C.h0b += 0.5e-3 * h1b;
-      } else {  // h1 = (0.01 / max(d1, d2)) ** (1/5); Python's max keeps d1 on a tie
-        const bool take2 = d2 > d1;
-        const double mx = take2 ? d2 : d1, base = 0.01 / mx;
-        const double mxb = -(h1b * 0.2 * (double)h1 / base) * base / mx;
-        if (take2) d2b += mxb;
-        else d1b_ += mxb;
-      }
-      // d2 = |rms((f1 - f0) / scale) / h0|
-      const double r2 = (double)d2 * h0, r2b = d2b / h0;
-      C.h0b = (C.h0b - d2b * d2 / h0);
-      C.d1b = (d1b_);
-      float f1b = 0.f, f0bp = 0.f, scb = 0.f;
-      if (el && r2 > 0.0) {
-        const float y = tx(0), f0 = tk(0), f1 = tk(1);
-        const float scale = s_ra.atol + fabsf(y) * s_ra.rtol;
-        const float q2 = (f1 - f0) / scale;
-        const float q2b = (float)(r2b * (double)q2 / (s_ra.n_el * r2));
-        f1b = q2b / scale;
-        f0bp = -q2b / scale;
-        scb = -q2b * q2 / scale;
-      }
-      if (sl < D) {
-        kb[0][sl] = f1b;
-        E.f0bp = f0bp;
-        E.scb = scb;
-      }
-      C.d0b = 0.0;
-      (void)d0;
-    } else if (ev == 0) {
-      if (s_ra.base == 2) {  // the rest of _select_initial_step: d0 = rms(y0 / scale), d1 = rms(f0 / scale)
-        const float d0 = (float)s_ra.init_rec[0], d1 = (float)s_ra.init_rec[1];
-        if (el) {
-          const float y = tx(0), f0 = tk(0);
-          const float scale = s_ra.atol + fabsf(y) * s_ra.rtol;
-          const float q0 = y / scale, q1 = f0 / scale;
-          const float q0b = d0 > 0.f ? (float)(C.d0b * (double)q0 / (s_ra.n_el * d0)) : 0.f;
-          const float q1b = d1 > 0.f ? (float)(C.d1b * (double)q1 / (s_ra.n_el * d1)) : 0.f;
-          const float scb = E.scb - q0b * q0 / scale - q1b * q1 / scale;
-          const float sy = y > 0.f ? 1.f : (y < 0.f ? -1.f : 0.f);
-          E.ybc += q0b / scale + scb * s_ra.rtol * sy;
-          E.fbc += q1b / scale;
-        }
-      }
-      if (sl < D) kb[0][sl] = el ? E.fbc : 0.f;
-    }
-    // this evaluation's output adjoint -> the layer-1 output slots
-    if (sl < D) g1s[tt * D + sl] = in_att ? kb[s][sl] : kb[0][sl];
-    vjp(ev);
-    // ---------------- after the VJP: the input adjoint ----------------
-    const float xb = sl < D ? gxs[tt * D + sl] : 0.f;
-    if (in_att) {
-      double v0 = 0.0, v1 = 0.0;
-      if (sl < D) {
-        const float X = xb + (s == 7 ? E.yb1 : 0.f);  // stage 7's input IS y1
-        E.yb0 += X;
-        float sb = 0.f;
-        for (int j = 1; j < s; ++j) {  // tableau row s - 2
-          const float c = s_beta[s - 2][j - 1];
-          kb[j][sl] += (c * C.dt32) * X;
-          sb += c * kk[j][sl];
-        }
-        E.dtb32 += X * sb;
-        if (s == 2) {  // attempt n done: the carries
-          E.ybc = el ? E.yb0 : 0.f;
-          E.fbc = el ? kb[1][sl] : 0.f;
-          v0 = el ? E.pd + (double)E.dtb32 : 0.0;
-          v1 = el ? E.pt : 0.0;
-        }
-      }
-      if (s == 2) {  // the grid sum of the attempt's d/d dt and d/d t0 terms
-        double S0, S1;
-        gsum(v0, v1, S0, S1);
-        C.dtbar = (C.dtb_base + (C.acc ? C.tbar : 0.0) + S0);
-        C.tbar = (C.tbar + S1);
-      }
-    } else if (ev == 1) {  // the probe: input y0 + h0 f0
-      const float f0 = el ? tk(0) : 0.f;
-      if (el) {
-        E.ybc += xb;
-        E.fbc += xb * C.h0f + E.f0bp;
-      }
-      double S0, S1;
-      gsum(el ? (double)(xb * f0) : 0.0, 0.0, S0, S1);
-      C.h0b = (C.h0b + S0);
-      const float d0 = (float)s_ra.init_rec[0], d1 = (float)s_ra.init_rec[1];
-      if (!(d0 < 1e-5f || d1 < 1e-5f)) {  // h0 = |0.01 d0 / d1|
-        C.d0b = (C.h0b * 0.01 / d1);
-        C.d1b = (C.d1b - C.h0b * (double)C.h0f / d1);
-      }
-    } else {  // evaluation 0: f(y0)
-      if (el) {
-        E.ybc += xb;
-        if (s_ra.gy0) s_ra.gy0[bi * D + sl] = E.ybc + s_ra.gsol[bi * D + sl];  // solution[0] = y0
-      }
-    }
-  }
-  float* part = a.part + ((int64_t)blockIdx.x * kTPB + wid) * a.nacc;
-  R0.template store<TPW>(part, lane);
-  R1.template store<TPW>(part + L0::AL.n, lane);
-  if (blockIdx.x == 0 && threadIdx.x == 0)
-    da.status[0] = (s_ab || __hip_atomic_load(dp_abort(da.gp), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) ? 4 : 0;
+  constexpr bool MP = TPW < 0;   // false, as a value-dependent constant: the MP statements are discarded
+#include "fetode_dopri_bwd_body.h"
 }
 
 // Parameter-gradient sums of one layer from the recorded adjoints (after fixed_bwd_kernel<ACC =
@@ -1986,8 +938,12 @@ static int64_t dopri_bwd_resident_wgs(const BwdEntry* e, bool one = false) {
     return -1;
   return (int64_t)per_cu[fi][v] * n_cu;
 }
+// fetode_integrate_dopri5_backward_set_shape: 0 automatic, 1 / 2 trajectories per wave
+static int g_dopri_bwd_shape = 0;
 // one trajectory per wave when that grid is resident (small batches), else e->dtpw
 static int dopri_bwd_tpw(const BwdEntry* e, int64_t B) {
+  if (g_dopri_bwd_shape == 1 && e->dopri1) return 1;
+  if (g_dopri_bwd_shape == 2) return e->dtpw;
   // (as fixed_tpw: while the one-per-wave grid fills at most half of its resident capacity)
   if (e->dopri1 && 2 * ((B + kTPB - 1) / kTPB) <= dopri_bwd_resident_wgs(e, true)) return 1;
   return e->dtpw;
@@ -1995,6 +951,35 @@ static int dopri_bwd_tpw(const BwdEntry* e, int64_t B) {
 static int64_t dopri_bwd_grid(const BwdEntry* e, int64_t B) {
   const int tpw = dopri_bwd_tpw(e, B);
   return (B + kTPB * tpw - 1) / (kTPB * tpw);
+}
+
+// multi-pass (fetode_dopri5_set_multipass): the virtual grid is the full-grid shape's, two
+// trajectories per wave; taken when that grid exceeds the test limit, or the one-grid launch of the
+// batch its co-resident capacity
+static int64_t dopri_bwd_mp_vgrid(int64_t B) { return (B + kTPB * 2 - 1) / (kTPB * 2); }
+static bool dopri_bwd_mp_forced(int64_t B) {
+  const int64_t limit = dp_grid_limit();
+  return dp_multipass() && B <= kDpMultipassMaxBatch && limit > 0 && dopri_bwd_mp_vgrid(B) > limit;
+}
+static bool dopri_bwd_use_mp(const BwdEntry* e, int64_t B) {
+  if (!dp_multipass() || B > kDpMultipassMaxBatch) return false;
+  if (dopri_bwd_mp_forced(B)) return true;
+  const bool one = dopri_bwd_tpw(e, B) == 1;
+  const int64_t resident = dopri_bwd_resident_wgs(e, one);
+  return resident >= 0 && dopri_bwd_grid(e, B) > resident;
+}
+// bytes of the one-grid workspace layout for a sweep grid of `grid` workgroups
+static int64_t dopri_bwd_ws_bytes(int64_t nacc, int64_t grid) {
+  const int64_t nrow = grid * kTPB, nch = nrow < kChunks ? nrow : kChunks;
+  const int64_t n = (int64_t)sizeof(unsigned) * kDpBarWords + (int64_t)sizeof(double) * (2 * grid + 4 * kDpGroups) +
+                    (int64_t)sizeof(double) * nacc * (nch + 1) + (int64_t)sizeof(float) * nrow * nacc;
+  return (n + 7) & ~(int64_t)7;
+}
+
+int fetode_integrate_dopri5_backward_set_shape(int tpw) {
+  const int prev = g_dopri_bwd_shape;
+  if (tpw >= 0 && tpw <= 2) g_dopri_bwd_shape = tpw;
+  return prev;
 }
 
 int64_t fetode_integrate_dopri5_backward_max_batch(const fetode_field_t* f) {
@@ -2020,8 +1005,13 @@ int64_t fetode_integrate_dopri5_backward_workspace(const fetode_field_t* f, int6
   layouts(f, &L0, &L1);
   const int64_t nacc = L0.n + L1.n, grid = dopri_bwd_grid(e, B), nrow = grid * kTPB;
   const int64_t nch = nrow < kChunks ? nrow : kChunks;
-  return (int64_t)sizeof(unsigned) * kDpBarWords + (int64_t)sizeof(double) * (2 * grid + 4 * kDpGroups) +
-         (int64_t)sizeof(double) * nacc * (nch + 1) + (int64_t)sizeof(float) * nrow * nacc;
+  const int64_t one_grid = (int64_t)sizeof(unsigned) * kDpBarWords + (int64_t)sizeof(double) * (2 * grid + 4 * kDpGroups) +
+                           (int64_t)sizeof(double) * nacc * (nch + 1) + (int64_t)sizeof(float) * nrow * nacc;
+  if (!dp_multipass() || B > kDpMultipassMaxBatch) return one_grid;
+  // multi-pass on: room for either launch — the virtual grid's layout, then the parking area
+  const int64_t vgrid = dopri_bwd_mp_vgrid(B);
+  const int64_t mp = dopri_bwd_ws_bytes(nacc, vgrid) + dopri_bwd_mp_park_bytes(f->ferro != nullptr, vgrid);
+  return one_grid > mp ? one_grid : mp;
 }
 
 int fetode_integrate_dopri5_backward(const fetode_field_t* f, const void* plan, int64_t B, const double* t, int32_t T,
@@ -2047,11 +1037,18 @@ int fetode_integrate_dopri5_backward(const fetode_field_t* f, const void* plan, 
     return fieldn_dopri5_backward(f, plan, B, t, T, rtol, atol, opts, tableau, grad_solution, tape, n_ev, attempts,
                                   n_att, init_rec, state0, init_mask, grad_y0, kan_grads, ferro_grads, workspace, status,
                                   stream);
-  const bool one = dopri_bwd_tpw(e, B) == 1;
-  const int64_t resident = dopri_bwd_resident_wgs(e, one);
-  if (resident < 0) return set_err(FETODE_EHIP, "dopri5 backward: occupancy query failed");
-  const int64_t grid = dopri_bwd_grid(e, B);
-  if (grid > resident)
+  const bool mp = dopri_bwd_use_mp(e, B);
+  const bool one = !mp && dopri_bwd_tpw(e, B) == 1;
+  const int64_t resident = mp ? dopri_bwd_mp_resident_wgs(f->ferro != nullptr) : dopri_bwd_resident_wgs(e, one);
+  if (resident <= 0) return set_err(FETODE_EHIP, "dopri5 backward: occupancy query failed");
+  // multi-pass: `grid` is the virtual grid (the leaf layout, the slots, the rows of partial sums);
+  // the launch takes pgrid <= the co-resident capacity (and the test limit) workgroups
+  const int64_t grid = mp ? dopri_bwd_mp_vgrid(B) : dopri_bwd_grid(e, B);
+  int64_t pgrid = grid;
+  if (mp) {
+    pgrid = grid < resident ? grid : resident;
+    if (dp_grid_limit() > 0 && pgrid > dp_grid_limit()) pgrid = dp_grid_limit();
+  } else if (grid > resident)
     return set_err(FETODE_EUNSUPPORTED, "dopri5 backward: batch %lld needs %lld workgroups, %lld resident",
                    (long long)B, (long long)grid, (long long)resident);
   hipStream_t s = (hipStream_t)stream;
@@ -2111,11 +1108,16 @@ int fetode_integrate_dopri5_backward(const fetode_field_t* f, const void* plan, 
   d.gp.slot = slot;
   d.gp.xs = xs;
   dp_single_device(d.gp, grid);
+  d.gp.mp = mp ? 1 : 0;
+  d.gp.park = mp ? (float*)((char*)workspace + dopri_bwd_ws_bytes(nacc, grid)) : nullptr;
   d.status = status;
   HIP_CHECK_RET(hipMemsetAsync(workspace, 0, sizeof(unsigned) * kDpBarWords, s));
   void* args[] = {&d};
-  HIP_CHECK_RET(resident_launch((const void*)(one ? e->dopri1 : e->dopri), dim3((unsigned)grid), dim3(64 * kTPB), args,
-                                0, s));
+  if (mp)
+    HIP_CHECK_RET(dopri_bwd_mp_launch(f->ferro != nullptr, &d, pgrid, s));
+  else
+    HIP_CHECK_RET(resident_launch((const void*)(one ? e->dopri1 : e->dopri), dim3((unsigned)grid), dim3(64 * kTPB), args,
+                                  0, s));
   const int64_t per = (nrow + nch - 1) / nch;
   hipLaunchKernelGGL(part_reduce_kernel, dim3(nblk(nacc, 64), (unsigned)nch), dim3(64), 0, s, part, nrow, nacc, per,
                      chunks);

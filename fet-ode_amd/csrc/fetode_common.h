@@ -82,6 +82,23 @@ int fieldn_dopri5_backward(const fetode_field_t* f, const void* plan, int64_t B,
 hipError_t resident_launch(const void* fn, dim3 grid, dim3 block, void** args, size_t lds, hipStream_t s);
 int resident_mode();
 extern int g_resident_mode;
+// Multi-pass mode of the resident LV dopri5 launches (fetode_dopri5_set_multipass, env
+// FETODE_DOPRI5_MULTIPASS; off by default) and the test cap on their physical workgroups
+// (fetode_dopri5_set_grid_limit; 0: occupancy only; no effect while the mode is off).
+int dp_multipass();
+int64_t dp_grid_limit();
+extern int g_dp_multipass;
+extern int64_t g_dp_grid_limit;
+// The largest batch of a multi-pass launch of the [2, 10, 2] kernels: the sweep addresses a tape row
+// of 2 D + H = 14 floats by a 32-bit element offset b * 14 + c < 2^31 (the forward's offsets are
+// 64-bit, its workgroup and slot numbers 32-bit and smaller than this).
+constexpr int64_t kDpMultipassMaxBatch = ((int64_t)1 << 31) / 14;
+// the multi-pass reverse sweep (fetode_bwd_mp.hip; ferro: the KAN-FET instantiation, else KAN): its
+// co-resident workgroups (-1: query failed), the bytes of its parking area for `vgrid` virtual
+// workgroups, and its launch (dopri_bwd_args: the DopriBwdArgs of fetode_bwd_dev.h)
+int64_t dopri_bwd_mp_resident_wgs(bool ferro);
+int64_t dopri_bwd_mp_park_bytes(bool ferro, int64_t vgrid);
+hipError_t dopri_bwd_mp_launch(bool ferro, void* dopri_bwd_args, int64_t grid, hipStream_t s);
 
 // The factored gate exp(gs(x+Ec)) = exp(gs x) * exp(gs Ec) is used only when
 // |gs*log2e*Ec| <= kFactorLimit everywhere in the layer: then exp(gs x) overflowing /

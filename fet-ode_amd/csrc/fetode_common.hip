@@ -22,6 +22,17 @@ int resident_mode() {
   return g_resident_mode;
 }
 
+int g_dp_multipass = -1;
+int64_t g_dp_grid_limit = 0;
+int dp_multipass() {
+  if (g_dp_multipass < 0) {
+    const char* v = getenv("FETODE_DOPRI5_MULTIPASS");
+    g_dp_multipass = v && atoi(v) != 0;
+  }
+  return g_dp_multipass;
+}
+int64_t dp_grid_limit() { return dp_multipass() ? g_dp_grid_limit : 0; }
+
 hipError_t resident_launch(const void* fn, dim3 grid, dim3 block, void** args, size_t lds, hipStream_t s) {
   if (resident_mode()) return hipLaunchCooperativeKernel(fn, grid, block, args, (unsigned)lds, s);
   return hipLaunchKernel(fn, grid, block, args, lds, s);
@@ -278,6 +289,18 @@ int32_t fetode_resident_launch_mode(int32_t mode) {
   return prev;
 }
 int fetode_abi_version(void) { return FETODE_ABI_VERSION; }
+
+int fetode_dopri5_set_multipass(int on) {
+  const int prev = fetode::dp_multipass();
+  if (on >= 0) fetode::g_dp_multipass = on != 0;
+  return prev;
+}
+
+int64_t fetode_dopri5_set_grid_limit(int64_t workgroups) {
+  const int64_t prev = fetode::g_dp_grid_limit;
+  fetode::g_dp_grid_limit = workgroups > 0 ? workgroups : 0;
+  return prev;
+}
 
 int32_t fetode_state_width(const fetode_field_t* f) {
   if (!f || !f->ferro) return 0;

@@ -378,687 +378,19 @@ __device__ __forceinline__ float v4_edges(const V4Lds<IN, FLEN>& L, const float*
 // per evaluation where the waves do not fill the SIMDs.
 template <int H, int K_, int NB, int NG, bool FERRO, bool HOT, bool DOPRI = false, bool TAPE = false, int TPW = 2>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void fused4_kernel(FusedArgs a) {
-  constexpr int D = 2, NI = NG - 1, NFL = 1 + NB, NFP = (NFL + 1) & ~1, K = FERRO ? K_ : 0;
-  // feature jobs: logistic 0..NB-1, SiLU, [gate, exp(gs x)], then x / u / m stores
-  constexpr int J_SILU = NB, J_GATE = NB + 1, J_EXP = NB + 2, J_X = FERRO ? NB + 3 : NB + 1;
-  constexpr int J_M = J_X + 1;
-  static_assert(J_M < 16 && NG <= 16, "v4 layout: NB logistic + SiLU (+ gate, exp) + x, m jobs on a row of 16 lanes");
-  static_assert(H <= 10, "v4 layout: H <= 10 groups of 3 lanes");
-  static_assert(!FERRO || K % 2 == 0, "v4 pairs Ferro elements (i, k), (i, k+1)");
-  constexpr int KP = K / 2 > 0 ? K / 2 : 1;
-  static_assert(TPW == 2 || (TPW == 1 && HOT && !DOPRI), "one trajectory per wave: the rk4 path");
-  constexpr int NLG = TPW == 2 ? 3 : 6;                      // lanes per hidden unit
-  // layer 0 (2 -> H): output o on a group of 3 lanes; layer 1 (H -> 2): hidden INPUT o on the
-  // same group (v7): its features, its Ferro elements of both outputs (pairs (o, 0, k), (o, 1, k):
-  // one packed pair feeds both output sums) and its two spline edges stay in the group's
-  // registers — no LDS exchange between layer 0 and layer 1
-  using FS0 = FerroSplit<D * KP, NLG>;
-  static_assert(!FERRO || D == 2, "v7 layer 1 pairs the two outputs of an input");
-  constexpr int REM1 = K % NLG;
-  constexpr bool SPLIT1 = TPW == 2 && REM1 == 1;             // one k left: two singles (d = 0, 1)
-  constexpr int NPL0 = FERRO ? FS0::NPL : 0, NPL1 = FERRO ? (SPLIT1 ? K / NLG : (K + NLG - 1) / NLG) : 0;
-  constexpr int NSL0 = FERRO ? FS0::NSL : 0, NSL1 = (FERRO && SPLIT1) ? 1 : 0;
-  constexpr int FPL0 = ((D * NFP + NLG - 1) / NLG + 3) & ~3;
-  constexpr int RF1 = (NFL + NLG - 1) / NLG;                 // feature rounds of a hidden input (SiLU + NB)
-  constexpr int FLEN0 = (NLG * FPL0 > D * NFP ? NLG * FPL0 : D * NFP);
-  if constexpr (DOPRI) {
-    if (a.dp.xr_world > 1 && blockIdx.x == gridDim.x - 1) {   // the cross-rank exchange workgroup
-      xrank_comm(a.dp);
-      return;
-    }
-  }
-  constexpr int KT = (NG + 2) / 3;                   // knots per group lane
-  static_assert(3 * KT >= NG, "knots per group lane");
-  // edge cubic tables by interval, one row of NI + 1 float4 per edge padded to SPR: at a pitch of 12
-  // float4 the rows of units 4 apart (layer 1) / of the same parity (layer 0) start on the same
-  // 16-byte slot of the bank row and the lanes' interval reads collide (35 % of the kernel's LDS
-  // cycles were conflicts, profiles/r06_lds_bench_nores.txt)
-  constexpr int SPR = NI + 2, SPE = (NI + 1) * 4;
-  constexpr int SPT0 = H * D * SPR * 4, SPT1 = D * H * SPR * 4;
+  constexpr bool MP = false;
+#include "fetode_fused4_body.h"
+}
 
-  __shared__ __attribute__((aligned(16))) float s_sp0[SPT0];
-  __shared__ __attribute__((aligned(16))) float s_sp1[SPT1];
-  __shared__ __attribute__((aligned(8))) f2 s_kr0[D * (NI + 1)], s_kr1[H * SPR];
-  __shared__ float s_c0[H], s_c1[D];
-  __shared__ __attribute__((aligned(16))) V4Lds<D, FLEN0> s_L0[TPW];
-
-  const int tid = threadIdx.x;
-  const int hh = tid >> 5;                                   // half-wave
-  const int g = TPW == 2 ? hh : 0, lane = tid & 31, row = lane >> 4, c1 = lane & 15;
-  const int64_t b = (int64_t)blockIdx.x * TPW + g;
-  const bool own = TPW == 2 || hh == 0;                      // TPW 1: half 0 stores
-  const bool valid = b < a.B;
-  V4Lds<D, FLEN0>& L0 = s_L0[g];
-
-  for (int i = tid; i < H * D * SPE; i += 64) s_sp0[(i / SPE) * SPR * 4 + i % SPE] = a.plan[a.P0.sp + i];
-  for (int i = tid; i < D * H * SPE; i += 64) s_sp1[(i / SPE) * SPR * 4 + i % SPE] = a.plan[a.P1.sp + i];
-  for (int i = tid; i < D * (NI + 1); i += 64) {
-    const int in = i / (NI + 1), m = i % (NI + 1);
-    s_kr0[i] = m < NI ? f2{a.plan[a.P0.knots + in * NG + m], a.plan[a.P0.rh + in * NI + m]} : f2{0.f, 0.f};
-  }
-  for (int i = tid; i < H * (NI + 1); i += 64) {
-    const int in = i / (NI + 1), m = i % (NI + 1);
-    s_kr1[in * SPR + m] = m < NI ? f2{a.plan[a.P1.knots + in * NG + m], a.plan[a.P1.rh + in * NI + m]} : f2{0.f, 0.f};
-  }
-  for (int i = tid; i < H; i += 64) s_c0[i] = a.plan[a.P0.fconst + i];
-  for (int i = tid; i < D; i += 64) s_c1[i] = a.plan[a.P1.fconst + i];
-  for (int i = lane; i < FLEN0; i += 32) L0.F[i] = 0.f;  // pads stay zero (finite x zero weight)
-
-  const bool fact = FERRO && a.plan[a.P0.flag] <= a.factor_limit && a.plan[a.P1.flag] <= a.factor_limit;
-  const float l2 = FETODE_LOG2E;
-
-  // ---- layer-0 edge lane: output o0 = 5 row + q/3, part cc0 ----
-  const int q = c1;
-  const int o0 = row * 5 + q / 3, cc0 = q % 3;
-  const bool act0 = q < 15 && o0 < H;
-  const int o0c = act0 ? o0 : 0;
-  const int gl = TPW == 2 ? cc0 : cc0 + 3 * hh;              // lane within the hidden unit's group
-  f2 ep0[NPL0 > 0 ? NPL0 : 1], k20[NPL0 > 0 ? NPL0 : 1], kE0[NPL0 > 0 ? NPL0 : 1], cp0[NPL0 > 0 ? NPL0 : 1];
-  int gi0[NPL0 > 0 ? NPL0 : 1];
-#pragma unroll
-  for (int r = 0; r < NPL0; ++r) {
-    const int P = gl * NPL0 + r;
-    const bool ok = act0 && P < D * KP;
-    int i = ok ? P / KP : 0;
-    asm volatile("" : "+v"(i));  // keep in a VGPR (no per-evaluation rematerialisation)
-    gi0[r] = i;
-    float t[4][2];
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const int64_t idx = (int64_t)o0c * (D * K) + i * K + (ok ? (P % KP) * 2 + h : 0);
-      const float gec = ok ? a.plan[a.P0.fe_GEc + idx] : 0.f;
-      t[0][h] = fact ? ex2(gec) : gec;
-      t[1][h] = ok ? a.plan[a.P0.fe_k2 + idx] : 0.f;
-      t[2][h] = ok ? a.plan[a.P0.fe_k2Ec + idx] : 0.f;
-      t[3][h] = ok ? a.plan[a.P0.fe_CPs2 + idx] : 0.f;
-    }
-    ep0[r] = f2{t[0][0], t[0][1]};
-    k20[r] = f2{t[1][0], t[1][1]};
-    kE0[r] = f2{t[2][0], t[2][1]};
-    cp0[r] = f2{t[3][0], t[3][1]};
-  }
-  // layer-0 single: leftover element q = cc0 of pair NPL0 * 3 + q / 2
-  int gs0 = 0;
-  float es0 = 0.f, k2s0 = 0.f, kEs0 = 0.f, cps0 = 0.f;
-  if constexpr (NSL0 > 0) {
-    const int Pl = NPL0 * NLG + gl / 2;
-    const bool ok = act0 && gl < 2 * FS0::REM;
-    const int i = ok ? Pl / KP : 0;
-    const int64_t idx = (int64_t)o0c * (D * K) + i * K + (ok ? (Pl % KP) * 2 + gl % 2 : 0);
-    const float gec = ok ? a.plan[a.P0.fe_GEc + idx] : 0.f;
-    es0 = fact ? ex2(gec) : gec;
-    k2s0 = ok ? a.plan[a.P0.fe_k2 + idx] : 0.f;
-    kEs0 = ok ? a.plan[a.P0.fe_k2Ec + idx] : 0.f;
-    cps0 = ok ? a.plan[a.P0.fe_CPs2 + idx] : 0.f;
-    gs0 = i;
-    asm volatile("" : "+v"(gs0));
-  }
-  f2 fw0[FPL0 / 2];
-#pragma unroll
-  for (int f = 0; f < FPL0; f += 2) {
-    float w[2];
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const int qq = gl * FPL0 + f + h, i = qq / NFP, ff = qq % NFP;
-      w[h] = (act0 && i < D && ff < NFL) ? a.plan[a.P0.kw + (int64_t)o0c * (D * NFL) + i * NFL + ff] : 0.f;
-    }
-    fw0[f / 2] = f2{w[0], w[1]};
-  }
-  // ---- layer-1 (v7): hidden input o0 on its group; lane gl owns k = gl + NLG r ----
-  // pair r: elements (o0, d = 0, k) and (o0, d = 1, k): .x feeds output 0, .y output 1
-  f2 ep1[NPL1 > 0 ? NPL1 : 1], k21[NPL1 > 0 ? NPL1 : 1], kE1[NPL1 > 0 ? NPL1 : 1], cp1[NPL1 > 0 ? NPL1 : 1];
-#pragma unroll
-  for (int r = 0; r < NPL1; ++r) {
-    const int k = gl + NLG * r;
-    const bool ok = act0 && k < K;
-    float t[4][2];
-#pragma unroll
-    for (int d = 0; d < 2; ++d) {
-      const int64_t idx = (int64_t)d * (H * K) + o0c * K + (ok ? k : 0);
-      const float gec = ok ? a.plan[a.P1.fe_GEc + idx] : 0.f;
-      t[0][d] = fact ? ex2(gec) : gec;   // padding: ep = 1 (fact) / 0, k = 0: th = 0, cp = 0
-      t[1][d] = ok ? a.plan[a.P1.fe_k2 + idx] : 0.f;
-      t[2][d] = ok ? a.plan[a.P1.fe_k2Ec + idx] : 0.f;
-      t[3][d] = ok ? a.plan[a.P1.fe_CPs2 + idx] : 0.f;
-    }
-    ep1[r] = f2{t[0][0], t[0][1]};
-    k21[r] = f2{t[1][0], t[1][1]};
-    kE1[r] = f2{t[2][0], t[2][1]};
-    cp1[r] = f2{t[3][0], t[3][1]};
-  }
-  // the single left over when K % 3 == 1: element (o0, d = cc0, K - 1) on lanes cc0 = 0, 1
-  float es1 = 0.f, k2s1 = 0.f, kEs1 = 0.f, cps1 = 0.f;
-  if constexpr (NSL1 > 0) {
-    const bool ok = act0 && cc0 < D;
-    const int64_t idx = (int64_t)(ok ? cc0 : 0) * (H * K) + o0c * K + (K - 1);
-    const float gec = ok ? a.plan[a.P1.fe_GEc + idx] : 0.f;
-    es1 = fact ? ex2(gec) : gec;
-    k2s1 = ok ? a.plan[a.P1.fe_k2 + idx] : 0.f;
-    kEs1 = ok ? a.plan[a.P1.fe_k2Ec + idx] : 0.f;
-    cps1 = ok ? a.plan[a.P1.fe_CPs2 + idx] : 0.f;
-  }
-  // lane cc0 = d < 2 also owns the spline edge (o0 -> d): the single / spline value goes to output d
-  const f2 dsel1 = f2{(act0 && gl == 0) ? 1.f : 0.f, (act0 && gl == 1) ? 1.f : 0.f};
-  // feature rounds: job j = cc0 + 3 r (logistic j < NB, SiLU j == NB), its weights for both outputs
-  float fna1[RF1], fab1[RF1], fml1[RF1];
-  f2 fwt1[RF1];
-#pragma unroll
-  for (int r = 0; r < RF1; ++r) {
-    const int j = gl + NLG * r;
-    const bool ok = act0 && j < NFL;
-    fna1[r] = 0.f; fab1[r] = 0.f; fml1[r] = 0.f;
-    const int ff = j < NB ? 1 + j : 0;   // kw feature index: SiLU 0, logistic j at 1 + j
-    if (ok && j < NB) {
-      fna1[r] = a.plan[a.P1.lg + 2 * (o0 * NB + j)];
-      fab1[r] = a.plan[a.P1.lg + 2 * (o0 * NB + j) + 1];
-    } else if (ok) {
-      fna1[r] = -l2;
-      fml1[r] = 1.f;   // SiLU: h * sigmoid(h)
-    }
-    fwt1[r] = ok ? f2{a.plan[a.P1.kw + (int64_t)0 * (H * NFL) + o0 * NFL + ff],
-                      a.plan[a.P1.kw + (int64_t)1 * (H * NFL) + o0 * NFL + ff]}
-                 : f2{0.f, 0.f};
-  }
-  // ---- layer-0 feature stream: input d = row, job c1 ----
-  float xna, xab, xmul, xadd;
-  float* xdst;
-  {
-    const int j = c1;
-    xna = 0.f; xab = 0.f; xmul = 1.f; xadd = 0.f;
-    xdst = &L0.sink;
-    if (j < NB) {
-      xna = a.plan[a.P0.lg + 2 * (row * NB + j)];
-      xab = a.plan[a.P0.lg + 2 * (row * NB + j) + 1];
-      xdst = &L0.F[row * NFP + 1 + j];
-    } else if (j == J_SILU) {
-      xna = -l2;
-      xdst = &L0.F[row * NFP];
-    } else if (FERRO && j == J_GATE) {
-      xna = -a.P0.gsl2e; xmul = -a.P0.wc; xadd = a.P0.wc;
-      xdst = &L0.G[row].y;
-    } else if (FERRO && j == J_EXP) {
-      xna = a.P0.gsl2e;
-      xdst = &L0.G[row].x;
-    } else if (j == J_X) {
-      xdst = &L0.G[row].z;
-    }
-  }
-  const bool x_silu = c1 == J_SILU, x_gate = FERRO && c1 == J_GATE, x_exp = FERRO && c1 == J_EXP;
-  const bool x_x = c1 == J_X;
-  // knot interval: lane c1 holds knot c1 (and 1/(knot c1+1 - knot c1)); the lane whose knot
-  // opens the interval writes u (no LDS round trip on the critical path)
-  const float xknot = c1 < NG ? a.plan[a.P0.knots + row * NG + c1] : __builtin_inff();
-
-  // knots of hidden input o0: lane cc0 holds knots KT cc0 .. KT cc0 + KT-1
-  float hknot[KT];
-#pragma unroll
-  for (int t = 0; t < KT; ++t) {
-    const int kk = KT * cc0 + t;
-    hknot[t] = (act0 && kk < NG) ? a.plan[a.P1.knots + o0 * NG + kk] : __builtin_inff();
-  }
-  // hysteresis state: prev_x of input `row` on the layer-0 gate lane, of input o0 on every lane
-  // of its group (each forms the gate itself) (ferro_class.py:409); per-layer contiguous blocks
-  // (include/fetode.h)
-  float prev0 = 0.f, prev1 = 0.f;
-  if (FERRO && valid) {
-    if (x_gate) prev0 = a.state[b * D + row];
-    if (act0) prev1 = a.state[a.B * D + b * H + o0];
-  }
-  bool re0 = FERRO && (a.init_mask & 1u), re1 = FERRO && (a.init_mask & 2u);
-
-  float y = valid ? a.y0[b * D + row] : 0.f;   // state dim `row`, replicated over the row
-  if (!a.single_eval && valid && own && c1 == 0) a.solution[b * D + row] = y;
-  __syncthreads();  // tables staged
-
-  STAMP_DECL
-  const float c0o = s_c0[o0c], c1o = s_c1[row];  // per-output constants, held in registers
-  const float* sp0_o = &s_sp0[o0c * D * SPR * 4];
-  // layer 1: the cubic table of edge (o0 -> d = cc0) and the (knot, 1/width) rows of input o0
-  const float* sp1_e = &s_sp1[((gl < D ? gl : 0) * H + o0c) * SPR * 4];
-  const f2* kr1_o = &s_kr1[o0c * SPR];
-  const int fofs0 = gl * FPL0;
-  const bool spl0 = act0 && gl < D;  // lanes owning a layer-0 spline edge (input si)
-  const int si0 = spl0 ? gl : 0;
-
-  // training tape: the two layer inputs of evaluation `ev` at tape[(ev B + b)(D + H) + c]
-  // TAPE = false (every inference instantiation) carries no tape code at all: the fixed-grid
-  // training forward and the dopri5 driver have taped instantiations of their own
-  bool taping = TAPE && a.tape != nullptr;
-  // the dopri5 tape holds the first tape_cap evaluations (the host re-runs a longer solve)
-  int64_t tape_left = DOPRI ? a.dp.tape_cap : 0;
-  // dopri5 training rows also hold the evaluation's output k after the two layer inputs
-  constexpr int TW = DOPRI ? 2 * D + H : D + H;
-  float* tape_b = taping ? a.tape + (valid ? b : 0) * TW : nullptr;
-  const int64_t tape_stride = a.B * TW;
-  uint64_t bal0 = 0;   // the feature phase's knot ballot (both trajectories' rows of both inputs)
-  auto eval_body = [&](float xin, auto fact_tag) __attribute__((always_inline)) -> float {
-    constexpr bool F_ = decltype(fact_tag)::value;
-    STAMP(6);
-    FETODE_MARK("X_FEAT");
-    {
-      // (1) layer-0 features of input `row`: one sigmoid-of-affine job per lane
-      const float pv = x_gate ? (re0 ? xin : prev0) : 0.f;
-      const float e = ex2(ffma(xna, xin - pv, xab));
-      const float sg = rcp(1.0f + e);
-      float val = ffma(sg, x_silu ? xin : xmul, xadd);
-      val = x_exp ? e : val;
-      val = x_x ? xin : val;
-      // knot intervals: lanes c1 < NG compare against their knot (the rest hold +inf); the edge
-      // lanes count their input's row of this ballot themselves (v4_edges)
-      bal0 = __builtin_amdgcn_ballot_w64(xin >= xknot);
-      *xdst = val;
-      if (FERRO) prev0 = xin;  // ferro_class.py:409 (meaningful on the gate lane)
-      re0 = false;
-    }
-    STAMP(0);
-    // the workgroup is this one wave: its LDS operations execute in order, so the edge reads see the
-    // feature writes with no wait on them (a wave barrier only keeps the compiler from reordering)
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    STAMP(0);
-    FETODE_MARK("EDGES0");
-    PRIO_LO();
-    // (2) layer-0 edges -> h_o on the group of 3
-    float h = v4_edges<D, FLEN0, NI, NPL0, NSL0, FPL0, FERRO, F_>(L0, sp0_o, s_kr0, gi0, ep0, k20, kE0, cp0, fw0,
-                                                                  fofs0, spl0, si0, a.P0.gsl2e, gs0, es0, k2s0, kEs0,
-                                                                  cps0, bal0, TPW == 2 ? 32 * g : 0);
-    if constexpr (TPW == 1) {   // the two halves' partial edge sums (the same sum on both halves)
-      float p = h, q2 = h;
-      permlane32_swap(p, q2);
-      h = p + q2;
-    }
-    PRIO_HI();
-    h = group3_sum(h, cc0) + c0o;   // lane 15 of a row (no group) is never read by a group
-    STAMP(2);
-    FETODE_MARK("H_FEAT");
-    // (3) layer 1 on the group of hidden input o0 (v7): partial sums of BOTH outputs in acc01
-    f2 acc01 = splat(0.0f);
-    {
-      // knot interval of h: KT compares per lane, summed over the group
-      // (a non-finite h counts 0 or all 12 knots: the zero row, no finiteness test needed)
-      const int mm = group3_sum_i(knot_count<KT>(h, hknot), cc0) - 1;
-      const int mfix = (unsigned)mm < (unsigned)NI ? mm : NI;
-      // spline operands by interval (the zero row NI holds (0, 0): u = 0 for finite h, NaN
-      // otherwise, as the reference's bases); their LDS latency hides under the pairs
-      const float4 cf = *reinterpret_cast<const float4*>(&sp1_e[mfix * 4]);
-      const f2 kw = kr1_o[mfix];
-      float sgl = 0.0f;
-      if constexpr (FERRO) {
-        // every lane of the group forms the gate and exp(gs h) of its input itself (three
-        // transcendentals: cheaper than broadcasting them across a group of 3 lanes)
-        const float pv = re1 ? h : prev1;
-        const float eg = ex2(ffma(-a.P1.gsl2e, h - pv, 0.0f));
-        const float w = ffma(rcp(1.0f + eg), -a.P1.wc, a.P1.wc);   // wc (1 - up)
-        const float e = F_ ? ex2(ffma(a.P1.gsl2e, h, 0.0f)) : 0.0f;
-        prev1 = h;   // ferro_class.py:409
-        re1 = false;
-        const f2 ew = f2{e, w}, xp = f2{h, 0.0f};
-        PRIO_LO();
-        if constexpr (NSL1 > 0) sgl = v4_single<F_>(ew, xp, es1, k2s1, kEs1, cps1, 0.0f, a.P1.gsl2e);
-#pragma unroll
-        for (int r = 0; r < NPL1; ++r) acc01 = v4_pair<F_>(ew, xp, ep1[r], k21[r], kE1[r], cp1[r], acc01, a.P1.gsl2e);
-      }
-      // the group's features (SiLU + NB logistic), each weighted for both outputs
-#pragma unroll
-      for (int r = 0; r < RF1; ++r) {
-        const float e = ex2(ffma(fna1[r], h, fab1[r]));
-        const float sg = rcp(1.0f + e);
-        const float val = fml1[r] != 0.0f ? h * sg : sg;   // SiLU h sigma(h) / logistic sigma
-        acc01 = pfma(fwt1[r], splat(val), acc01);
-      }
-      const float u = (h - kw.x) * kw.y;
-      const float sv = ffma(ffma(ffma(cf.w, u, cf.z), u, cf.y), u, cf.x);
-      acc01 = pfma(dsel1, splat(sgl + sv), acc01);   // lane d < 2: single + spline onto output d
-#ifndef FETODE_EXPERIMENT_NO_TAPE_STORE
-      // the evaluation's tape row in ONE non-temporal store: h_o from the group's first lane, x_row
-      // from the row's idle lane 15 (two plain stores cost the B = 4096 taped solve 23 us over none,
-      // this one 15: profiles/r06_tape_store_ab.log; the sweep reads the rows long after)
-      if (taping && valid && own && ((act0 && cc0 == 0) || q == 15))
-        __builtin_nontemporal_store(q == 15 ? xin : h, tape_b + (q == 15 ? row : D + o0));
-#endif
-    }
-    if (taping) {
-      tape_b += tape_stride;
-      if constexpr (DOPRI) taping = --tape_left > 0;
-    }
-    STAMP(3);
-    // output sums over the half-wave: the permlane16 swap folds the two rows of each output into
-    // row d (rows 0 / 2: output 0, rows 1 / 3: output 1), a row sum finishes: k_row on row `row`
-    PRIO_HI();
-    float p0 = acc01.x, p1 = acc01.y;
-    if constexpr (TPW == 1) {   // the two halves' partials first (the same sums on both halves)
-      float p = p0, q2 = p0;
-      permlane32_swap(p, q2);
-      p0 = p + q2;
-      float r = p1, t = p1;
-      permlane32_swap(r, t);
-      p1 = r + t;
-    }
-    permlane16_swap(p0, p1);
-    const float kr = row_sum16(p0 + p1) + c1o;
-    STAMP(5);
-    FETODE_MARK("END");
-    return kr;
-  };
-  // the step / output schedule is staged through LDS in chunks: per-step global loads in the
-  // loop would wait (vmcnt) behind the solution stores of the previous step
-  constexpr int SCH = 32;
-  __shared__ float s_dt[SCH], s_hh[SCH], s_h6[SCH], s_oslope[SCH];
-  __shared__ int s_ostep[SCH], s_omode[SCH];
-  auto load_steps = [&](int s0) {
-    __syncthreads();
-    for (int i = tid; i < SCH && s0 + i < a.n_steps; i += 64) {
-      s_dt[i] = a.step_coef[4 * (s0 + i) + 0];
-      s_hh[i] = a.step_coef[4 * (s0 + i) + 1];
-      s_h6[i] = a.step_coef[4 * (s0 + i) + 2];
-    }
-    __syncthreads();
-  };
-  auto load_outs = [&](int j0) {
-    __syncthreads();
-    for (int i = tid; i < SCH; i += 64) {
-      const bool in = j0 + i < a.T;
-      s_ostep[i] = in ? a.out_step[j0 + i] : -1;
-      s_omode[i] = in ? a.out_mode[j0 + i] : 1;
-      s_oslope[i] = in ? a.out_slope[j0 + i] : 0.f;
-    }
-    __syncthreads();
-  };
-
-  auto out_write = [&](int j, float v) __attribute__((always_inline)) {
-#ifndef FETODE_EXPERIMENT_NO_OUT
-    if (valid && own && c1 == 0) a.solution[((int64_t)j * a.B + b) * D + row] = v;
-#endif
-  };
-  using FT = std::integral_constant<bool, true>;
-  using FF = std::integral_constant<bool, false>;
-
-  if constexpr (HOT) {
-    // rk4 (torchdiffeq rk_common.rk4_alt_step_func op order); the step's first two output
-    // slots are read before its stages and consumed after them, with predicated stores
-    int sb = 0, jb = 1, jj = 1;
-    load_steps(0);
-    load_outs(1);
-    auto run = [&](auto fact_tag) __attribute__((always_inline)) {
-      const float third = 1.0f / 3.0f;
-      for (int s = 0; s < a.n_steps; ++s) {
-        if (s - sb == SCH) {
-          sb = s;
-          load_steps(s);
-        }
-        if (jj + 1 - jb >= SCH) {
-          jb = jj;
-          load_outs(jj);
-        }
-        const int sr = s - sb, jr = jj - jb;
-        const float dt = s_dt[sr];
-        const int os0 = s_ostep[jr], os1 = s_ostep[jr + 1], om0 = s_omode[jr];
-        const float osl0 = s_oslope[jr];
-        STAMP(7);
-        const float k1 = eval_body(y, fact_tag);
-        const float k2 = eval_body(y + (dt * k1) * third, fact_tag);
-        const float k3 = eval_body(y + dt * (k2 - k1 * third), fact_tag);
-        const float k4 = eval_body(y + dt * ((k1 - k2) + k3), fact_tag);
-        const float y1 = y + (((k1 + 3.0f * (k2 + k3)) + k4) * dt) * 0.125f;
-        if (os0 == s) {
-          // mode / slope as opaque VGPRs: VALU selects instead of scalar branches on the mode
-          int m0 = om0;
-          float sl0 = osl0;
-          asm volatile("" : "+v"(m0), "+v"(sl0));
-          const float oip = y + sl0 * (y1 - y);
-          const float o1 = m0 == 1 ? y1 : oip;
-          out_write(jj, m0 == 0 ? y : o1);
-          ++jj;
-          if (os1 == s) {  // several outputs inside one step (step_size grids)
-            while (jj < a.T) {
-              if (jj - jb == SCH) {
-                jb = jj;
-                load_outs(jj);
-              }
-              if (s_ostep[jj - jb] != s) break;
-              const int mode = s_omode[jj - jb];
-              out_write(jj, mode == 0 ? y : (mode == 1 ? y1 : y + s_oslope[jj - jb] * (y1 - y)));
-              ++jj;
-            }
-          }
-        }
-        STAMP(1);
-        y = y1;
-      }
-    };
-    if (fact) run(FT{});
-    else run(FF{});
-  } else {
-    auto eval = [&](float xin) __attribute__((always_inline)) -> float {
-      if (fact) return eval_body(xin, FT{});
-      return eval_body(xin, FF{});
-    };
-    if constexpr (DOPRI) {
-      // the whole driver once per coercive-gate form (as the rk4 path): the evaluations inline
-      // one specialised field body, not a runtime choice between two per evaluation
-      auto drive = [&](auto fact_tag) __attribute__((always_inline)) {
-#ifndef FETODE_EXP_NO_EVAL
-        auto eval = [&](float xin) __attribute__((always_inline)) -> float { return eval_body(xin, fact_tag); };
-#else   // diagnostics only: a trivial field, the reductions and control as is
-        auto eval = [&](float xin) -> float { return -0.5f * xin; };
-#endif
-        // ---- device-resident dopri5 (dopri5.py _Dopri5, lane (traj, dim = row) carries y_row) ----
-        const DopriParams& P = a.dp;
-        const bool real = valid && c1 == 0;  // one lane per (trajectory, state dim) in the sums
-        const double n_el = P.n_total;   // B * D, or the global batch's in a sharded solve
-        int nfev = 0, n_att = 0, status = 0;
-        unsigned round = 0;
-        auto gsum2 = [&](double v0, double v1, double& s0, double& s1) {
-#pragma unroll
-          for (int o = 32; o > 0; o >>= 1) {
-            v0 += __shfl_xor(v0, o);
-            v1 += __shfl_xor(v1, o);
-          }
-          if (grid_sum2(P, round, v0, v1, s0, s1)) status = 4;
-        };
-        // training: the output of evaluation nfev (the first tape_cap of them) next to its layer
-        // inputs, in the row the evaluation just wrote (tape_b has moved past it)
-        auto ktape = [&](float k) {
-          if constexpr (TAPE)
-            if (nfev < P.tape_cap && valid && c1 == 0) tape_b[D + H + row - tape_stride] = k;
-        };
-        float f0 = eval(y);
-        ktape(f0);
-        ++nfev;
-        double dt;
-        if (P.first_step > 0.0) {
-          dt = P.first_step;
-        } else {  // misc._select_initial_step in fp32 (dopri5.py select_initial_step)
-          const float scale = P.atol + P.rtol * fabsf(y);
-          const float q0 = y / scale, q1 = f0 / scale;
-          double s, s1;
-          gsum2(real ? (double)q0 * q0 : 0.0, real ? (double)q1 * q1 : 0.0, s, s1);
-          const float d0 = fabsf(sqrtf((float)(s / n_el)));
-          const float d1 = fabsf(sqrtf((float)(s1 / n_el)));
-          float h0 = (d0 < 1e-5f || d1 < 1e-5f) ? 1e-6f : (0.01f * d0) / d1;
-          h0 = fabsf(h0);
-          const float f1 = eval(y + f0 * h0);
-          ktape(f1);
-          ++nfev;
-          const float q2 = (f1 - f0) / scale;
-          gsum2(real ? (double)q2 * q2 : 0.0, 0.0, s, s1);
-          const float d2 = fabsf(sqrtf((float)(s / n_el)) / h0);
-          float h1;
-          if (d1 <= 1e-15f && d2 <= 1e-15f) h1 = fmaxf(1e-6f, h0 * 1e-3f);
-          else h1 = (float)pow((double)(0.01f / fmaxf(d1, d2)), (double)0.2f);  // fp64 pow rounded once: host == device
-          dt = (double)fminf(100.0f * h0, fabsf(h1));
-          if (TAPE && blockIdx.x == 0 && tid == 0) {
-            P.init_rec[0] = d0;
-            P.init_rec[1] = d1;
-            P.init_rec[2] = d2;
-            P.init_rec[3] = h0;
-            P.init_rec[4] = h1;
-          }
-        }
-        float co[5] = {y, 0.f, 0.f, 0.f, 0.f};
-        double t0s = P.t[0], t1s = P.t[0];
-        for (int i = 1; i < P.T && status == 0; ++i) {
-          const double next_t = P.t[i];
-          int n_steps = 0;
-          while (next_t > t1s) {
-            if (n_steps >= P.max_steps) { status = 3; break; }
-            const double t0 = t1s;
-            if (!(t0 + dt > t0)) { status = 2; break; }
-            const float dt32 = (float)dt;
-            const double t1 = t0 + dt;
-            // rk_common._runge_kutta_step in fetode_lincomb's op order, accumulated as the stages
-            // arrive: A[i] is stage s+1+i's sum k0 c0 + k1 c1 + ... (the same left-to-right sums)
-            float A[6];
-#pragma unroll
-            for (int q = 0; q < 6; ++q) A[q] = f0 * (P.stc[0][q] * dt32);
-            float err = f0 * (P.stc[0][6] * dt32);
-            float mid = f0 * (P.stc[0][7] * dt32);
-            float yi = y, kn = f0;
-#pragma unroll 1
-            for (int st = 0; st < 6; ++st) {
-              yi = y + A[0];
-              // stage column st + 1 into SGPRs before the evaluation (the loads complete under it)
-              float c[8];
-#pragma unroll
-              for (int q = 0; q < 8; ++q) c[q] = P.stc[st + 1][q];
-              kn = eval(yi);
-              ktape(kn);
-              ++nfev;
-              // entries past the tableau (coefficient 0) are never read again
-#pragma unroll
-              for (int q = 0; q < 5; ++q) A[q] = A[q + 1] + kn * (c[q] * dt32);
-              err = err + kn * (c[6] * dt32);
-              mid = mid + kn * (c[7] * dt32);
-              STAMP(6);
-            }
-            const float y1 = yi;
-            const float tol = P.atol + P.rtol * fmaxf(fabsf(y), fabsf(y1));
-            const float qe = err / tol;
-            double s, nbad;
-            gsum2(real ? (double)qe * qe : 0.0, (real && !__builtin_isfinite(y)) ? 1.0 : 0.0, s, nbad);
-            STAMP(1);
-            if (status) break;
-            if (nbad != 0.0) { status = 1; break; }
-            const float ratio = sqrtf((float)(s / n_el));
-            const bool accept = ratio <= 1.0f;
-            if (blockIdx.x == 0 && tid == 0 && n_att < P.max_att) {
-              double* o = P.att + (int64_t)n_att * 4;
-              o[0] = t0;
-              o[1] = dt;
-              o[2] = (double)ratio;
-              o[3] = accept ? 1.0 : 0.0;
-            }
-            ++n_att;
-            if (accept) {  // interp._interp_fit (fetode_interp_fit's op order)
-              const float ym = y + mid, fa = f0, fb6 = kn;
-              co[4] = ((2.0f * dt32) * (fb6 - fa) - 8.0f * (y1 + y)) + 16.0f * ym;
-              co[3] = ((dt32 * (5.0f * fa - 3.0f * fb6) + 18.0f * y) + 14.0f * y1) - 32.0f * ym;
-              co[2] = ((dt32 * (fb6 - 4.0f * fa) - 11.0f * y) - 5.0f * y1) + 16.0f * ym;
-              co[1] = dt32 * fa;
-              co[0] = y;
-              y = y1;
-              f0 = kn;
-              t0s = t0;
-              t1s = t1;
-            } else {
-              t0s = t0;
-            }
-            // rk_common._optimal_step_size in fp64 (dopri5.py optimal_step)
-            const double rr = (double)ratio;
-            double nxt;
-            if (rr == 0.0) {
-              nxt = dt * P.ifactor;
-            } else {
-              const double dfac = rr < 1.0 ? 1.0 : P.dfactor;
-              const double factor = __builtin_isnan(rr) ? rr : fmin(P.ifactor, fmax(P.safety / pow(rr, 1.0 / 5.0), dfac));
-              nxt = dt * factor;
-            }
-            dt = __builtin_isnan(nxt) ? nxt : fmin(fmax(nxt, P.min_step), P.max_step);
-            ++n_steps;
-            STAMP(7);
-          }
-          if (status) break;
-          const float xq = (float)((next_t - t0s) / (t1s - t0s));  // interp._interp_evaluate
-          float total = co[0] + xq * co[1];
-          float xp = xq;
-#pragma unroll
-          for (int j = 2; j < 5; ++j) {
-            xp = xp * xq;
-            total = total + xp * co[j];
-          }
-          out_write(i, total);
-        }
-        if (P.xr_world > 1 && blockIdx.x == 0 && tid == 0)   // the exchange workgroup may stop
-          __hip_atomic_store(dp_fin(P), round + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (blockIdx.x == 0 && tid == 0) {
-          P.stats[0] = nfev;
-          P.stats[1] = n_att;
-          P.stats[2] = __hip_atomic_load(P.bar + kDpLine * (kDpGroups + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) ? 4 : status;
-        }
-      };
-      if (fact) drive(FT{});
-      else drive(FF{});
-    } else if (a.single_eval) {
-      const float f = eval(y);
-      if (valid && c1 == 0) a.eval_out[b * D + row] = f;
-    } else {
-      const int ns = a.method == FETODE_RK4 || a.method == FETODE_RK4_CLASSIC ? 4
-                     : a.method == FETODE_MIDPOINT ? 2 : 1;
-      const float third = 1.0f / 3.0f;
-      int sb = 0, jb = 1, jj = 1;
-      load_steps(0);
-      load_outs(1);
-      for (int s = 0; s < a.n_steps; ++s) {
-        if (s - sb == SCH) {
-          sb = s;
-          load_steps(s);
-        }
-        const float dt = s_dt[s - sb], hh = s_hh[s - sb], h6 = s_h6[s - sb];
-        float k1 = 0.f, k2 = 0.f, k3 = 0.f, k4 = 0.f;
-        for (int st = 0; st < ns; ++st) {
-          float xin = y;
-          if (a.method == FETODE_RK4) {
-            if (st == 1) xin = y + (dt * k1) * third;
-            else if (st == 2) xin = y + dt * (k2 - k1 * third);
-            else if (st == 3) xin = y + dt * ((k1 - k2) + k3);
-          } else if (a.method == FETODE_RK4_CLASSIC) {
-            if (st == 1) xin = y + hh * k1;
-            else if (st == 2) xin = y + hh * k2;
-            else if (st == 3) xin = y + dt * k3;
-          } else if (a.method == FETODE_MIDPOINT) {
-            if (st == 1) xin = y + k1 * hh;
-          }
-          const float kk = eval(xin);
-          if (st == 0) k1 = kk;
-          else if (st == 1) k2 = kk;
-          else if (st == 2) k3 = kk;
-          else k4 = kk;
-        }
-        float y1;
-        if (a.method == FETODE_RK4) y1 = y + (((k1 + 3.0f * (k2 + k3)) + k4) * dt) * 0.125f;
-        else if (a.method == FETODE_RK4_CLASSIC) y1 = y + h6 * (((k1 + 2.0f * k2) + 2.0f * k3) + k4);
-        else if (a.method == FETODE_MIDPOINT) y1 = y + dt * k2;
-        else y1 = y + dt * k1;
-        while (jj < a.T) {
-          if (jj - jb == SCH) {
-            jb = jj;
-            load_outs(jj);
-          }
-          if (s_ostep[jj - jb] != s) break;
-          const int mode = s_omode[jj - jb];
-          out_write(jj, mode == 0 ? y : (mode == 1 ? y1 : y + s_oslope[jj - jb] * (y1 - y)));
-          ++jj;
-        }
-        y = y1;
-      }
-    }
-  }
-  if (FERRO && valid && own) {
-    if (x_gate) a.state[b * D + row] = prev0;
-    if (act0 && cc0 == 0) a.state[a.B * D + b * H + o0] = prev1;
-  }
-  STAMP_FLUSH();
+// The multi-pass resident dopri5 driver (the body's MP branch): the grid is at most the co-resident
+// capacity, each workgroup serves ceil(virtual grid / grid) virtual workgroups between two grid sums.
+// (the taped KAN-FET instantiation may take one wave per SIMD: at two its register allocation needs
+// scratch; the launch is sized by the occupancy reached, fewer resident waves only mean more passes)
+template <int H, int K_, int NB, int NG, bool FERRO, bool TAPE>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(FERRO && TAPE ? 1 : 2))) void fused4_mp_kernel(FusedArgs a) {
+  constexpr bool HOT = false, DOPRI = true, MP = true;
+  constexpr int TPW = 2;
+#include "fetode_fused4_body.h"
 }
 
 // =============================================================================================
@@ -1979,6 +1311,7 @@ struct FusedEntry {
   fused_fn rk4_v8;    // v8 rk4 at two waves per trajectory (inference, the strong-scaling shards)
   fused_fn rk4_v8x2;  // the same, two trajectories per four-wave workgroup
   fused_fn fn_tape, fn_rk4_tape, fn_rk4_1_tape;  // v4 / v7 recording the fixed-grid training tape
+  fused_fn dopri_mp, dopri_mp_tape;  // the multi-pass resident dopri5 driver (fused4_mp_kernel)
 };
 const FusedEntry kFused[] = {
     // LV KAN-FET [2,10,2], K=10 (train_kanfet_node_predprey.py:146)
@@ -1988,7 +1321,8 @@ const FusedEntry kFused[] = {
      small6_kernel<true, false, true, true>, small6_kernel<true, false, false, true>,
      small6_kernel<true, true, false, true>, fused4_kernel<10, 10, 10, 12, true, true, false, false, 1>,
      v8_kernel<true, 1>, v8_kernel<true, 2>, fused4_kernel<10, 10, 10, 12, true, false, false, true>,
-     fused4_kernel<10, 10, 10, 12, true, true, false, true>, fused4_kernel<10, 10, 10, 12, true, true, false, true, 1>},
+     fused4_kernel<10, 10, 10, 12, true, true, false, true>, fused4_kernel<10, 10, 10, 12, true, true, false, true, 1>,
+     fused4_mp_kernel<10, 10, 10, 12, true, false>, fused4_mp_kernel<10, 10, 10, 12, true, true>},
     // LV KAN [2,10,2] (predator_prey.py:101)
     {2, 10, 2, 1, 10, 12, false, fused4_kernel<10, 2, 10, 12, false, false>, fused4_kernel<10, 2, 10, 12, false, true>,
      small6_kernel<false, false>, small6_kernel<false, true>, fused4_kernel<10, 2, 10, 12, false, false, true>,
@@ -1996,7 +1330,8 @@ const FusedEntry kFused[] = {
      small6_kernel<false, false, true, true>, small6_kernel<false, false, false, true>,
      small6_kernel<false, true, false, true>, fused4_kernel<10, 2, 10, 12, false, true, false, false, 1>,
      v8_kernel<false, 1>, v8_kernel<false, 2>, fused4_kernel<10, 2, 10, 12, false, false, false, true>,
-     fused4_kernel<10, 2, 10, 12, false, true, false, true>, fused4_kernel<10, 2, 10, 12, false, true, false, true, 1>},
+     fused4_kernel<10, 2, 10, 12, false, true, false, true>, fused4_kernel<10, 2, 10, 12, false, true, false, true, 1>,
+     fused4_mp_kernel<10, 2, 10, 12, false, false>, fused4_mp_kernel<10, 2, 10, 12, false, true>},
 };
 
 // Batches up to kSmallMax take v6 (one trajectory per 3-wave workgroup, latency-bound chain split
@@ -2599,9 +1934,19 @@ int fetode_field_forward(const fetode_field_t* f, const void* plan, const float*
   return launch_fused(f, a, stream);
 }
 
-int64_t fetode_integrate_dopri5_workspace(int64_t B) {
+static int64_t dopri5_workspace_base(int64_t B) {
   const int64_t grid = B;  // v6 (one trajectory per workgroup) at small batches, v4 (two) beyond
   return (int64_t)sizeof(unsigned) * kDpBarWords + (int64_t)sizeof(double) * (2 * grid + 4 * kDpGroups + 4);
+}
+int64_t fetode_integrate_dopri5_workspace(int64_t B) {
+  // multi-pass: + the forward's parking area, (virtual grid, 5, 64) floats
+  return dopri5_workspace_base(B) + (dp_multipass() ? (int64_t)sizeof(float) * 5 * 64 * nblk(B, 2) : 0);
+}
+
+int64_t fetode_integrate_dopri5_multipass_max_batch(const fetode_field_t* f) {
+  if (validate_field(f) != FETODE_OK) return 0;
+  const FusedEntry* e = find_fused(f);
+  return e && e->dopri_mp ? kDpMultipassMaxBatch : 0;
 }
 
 // every workgroup must be resident at once (grid reductions): one-wave workgroups of two
@@ -2630,6 +1975,21 @@ static int64_t dopri5_resident_wgs(const FusedEntry* e, bool ferro) {
   }
   if (!per_cu[fi] && hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu[fi], e->dopri, 64, 0) != hipSuccess) return -1;
   return (int64_t)per_cu[fi] * n_cu;
+}
+
+// the multi-pass driver's physical grid: its own occupancy (inference / taped)
+static int64_t dopri5_mp_resident_wgs(const FusedEntry* e, bool ferro, bool tape) {
+  static int n_cu = 0, per_cu[2][2] = {{0, 0}, {0, 0}};
+  const int fi = ferro ? 0 : 1, ti = tape ? 1 : 0;
+  if (!n_cu) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+      return -1;
+  }
+  if (!per_cu[fi][ti] &&
+      hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu[fi][ti], tape ? e->dopri_mp_tape : e->dopri_mp, 64, 0) != hipSuccess)
+    return -1;
+  return (int64_t)per_cu[fi][ti] * n_cu;
 }
 
 // fieldn's dopri5 driver: one trajectory per one-wave workgroup, every one resident
@@ -2684,14 +2044,25 @@ static int dopri5_launch(const fetode_field_t* f, const void* plan, const float*
   // small batches (the reference's own X0 (1, 2); the strong-scaled shard): v6, one trajectory per
   // workgroup, when the whole grid is resident; else v4, two per one-wave workgroup
   const int64_t res6 = (!fn && !sharded && B <= small_max()) ? dopri5_small_resident_wgs(e, f->ferro != nullptr) : -1;
-  const bool use6 = res6 >= B;
+  // multi-pass (fetode_dopri5_set_multipass): the v4 grid of this batch as the VIRTUAL grid of a
+  // launch of at most `limit` / the co-resident capacity workgroups, when it does not fit one grid
+  const bool mp_can = dp_multipass() && !fn && !sharded && B <= kDpMultipassMaxBatch;
+  const int64_t mp_limit = mp_can ? dp_grid_limit() : 0;
+  const bool mp_forced = mp_limit > 0 && nblk(B, 2) > mp_limit;
+  const bool use6 = res6 >= B && !mp_forced;
   const int64_t resident = fn ? dopri5_fieldn_resident_wgs(f->ferro != nullptr, tape_cap > 0)
                               : use6 ? res6 : dopri5_resident_wgs(e, f->ferro != nullptr);
   if (resident < 0) return set_err(FETODE_EHIP, "dopri5: occupancy query failed");
   const int per = fn ? 1 : 2;  // trajectories per workgroup (v6: one, never sharded)
   const int64_t grid = (use6 || fn) ? B : nblk(B, 2);
-  const int64_t lgrid = grid + (sharded ? 1 : 0);   // + the cross-rank exchange workgroup
-  if (lgrid > resident)
+  int64_t lgrid = grid + (sharded ? 1 : 0);   // + the cross-rank exchange workgroup
+  const bool mp = mp_can && (mp_forced || lgrid > resident);
+  if (mp) {   // the physical grid: never more than the multi-pass kernel's own occupancy
+    const int64_t res_mp = dopri5_mp_resident_wgs(e, f->ferro != nullptr, tape_cap > 0);
+    if (res_mp <= 0) return set_err(FETODE_EHIP, "dopri5: occupancy query failed");
+    lgrid = std::min(grid, res_mp);
+    if (mp_limit > 0) lgrid = std::min(lgrid, mp_limit);
+  } else if (lgrid > resident)
     return set_err(FETODE_EUNSUPPORTED, "dopri5: batch %lld needs %lld workgroups, %lld resident", (long long)B,
                    (long long)lgrid, (long long)resident);
   FusedArgs a;
@@ -2734,6 +2105,9 @@ static int dopri5_launch(const fetode_field_t* f, const void* plan, const float*
   P.att = attempts;
   P.max_att = attempts ? max_attempts : 0;
   P.xr_g = P.xs + 4 * kDpGroups;
+  // the parking area follows the one-grid workspace (fetode_integrate_dopri5_workspace)
+  P.mp = mp ? 1 : 0;
+  P.park = mp ? (float*)((char*)workspace + dopri5_workspace_base(B)) : nullptr;
   P.n_total = (double)B_total * f->kan[0].in_features;
   // leaves: runs of L workgroups; exact when this rank's workgroups are whole leaves of the
   // single-device grid over the global batch (two trajectories per workgroup everywhere)
@@ -2780,6 +2154,7 @@ static int dopri5_launch(const fetode_field_t* f, const void* plan, const float*
   HIP_CHECK_RET(hipMemsetAsync(workspace, 0, sizeof(unsigned) * kDpBarWords, s));
   void* args[] = {&a};
   const void* kfn = fn ? fieldn_dopri_fn(f->ferro != nullptr, a.tape != nullptr)
+                   : mp ? (const void*)(a.tape ? e->dopri_mp_tape : e->dopri_mp)
                    : use6 ? (const void*)(a.tape ? e->small_dopri_tape : e->small_dopri)
                           : (const void*)(a.tape ? e->dopri_tape : e->dopri);
   HIP_CHECK_RET(resident_launch(kfn, dim3((unsigned)lgrid), dim3(use6 ? 192 : 64), args, 0, s));

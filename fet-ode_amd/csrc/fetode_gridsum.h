@@ -40,6 +40,11 @@ struct DopriParams {
   // polls before a spin gives up (status 4); 0 = kDpSpinLimit / kXrSpinLimit.  A test knob
   // (fetode_dopri5_set_spin_limit): a tiny limit forces the timeout path on a healthy grid
   uint32_t spin_limit;
+  // multi-pass (fetode_dopri5_set_multipass): the launch's grid is smaller than the grid the leaf
+  // layout above describes (the VIRTUAL grid, nblk_global workgroups); physical workgroup p serves
+  // the virtual workgroups p, p + gridDim.x, ... in turn and parks what each carries across a sum
+  float* park;         // forward: (virtual grid, 5, 64) floats; sweep: (virtual waves, kMpElWords) words
+  int32_t mp;          // 1: a multi-pass launch
 };
 
 // the smallest power-of-two leaf length that needs <= kDpGroups leaves over nb workgroups
@@ -206,6 +211,95 @@ __device__ inline bool grid_sum2(const DopriParams& P, unsigned& round, double v
   }
   double u0 = 0.0, u1 = 0.0;
   if ((unsigned)lane < ngrp && !ab) dp_ld16(&xs[2 * lane], u0, u1);   // one device: leaves 0 .. ngrp-1
+  s0 = xor_sum64(u0);
+  s1 = xor_sum64(u1);
+  return ab != 0;
+}
+
+// Multi-pass form of grid_sum2: the reduction of round r over the VIRTUAL grid (P.nblk_global
+// workgroups, leaf layout dp_single_device(P, virtual grid)) when one physical workgroup stands for
+// several virtual ones.  grid_sum2_arrive, once per virtual workgroup v, stores v's partial in v's
+// slot and arrives on v's leaf counter; the arrival that completes a leaf sums it (the same lane-per-
+// partial xor tree) and bumps the top counter.  Arrivals never wait.  After its last arrival of the
+// round the physical workgroup calls grid_sum2_poll ONCE: the bounded spin on the top counter and
+// the sum of the leaf sums.  The result is the fp64 sum, in the same order, a single-pass launch of
+// the virtual grid forms.  Double buffering holds as in grid_sum2: a physical workgroup arrives
+// (for any of its virtual workgroups) at round r + 1 only after it has read round r.
+// The test knob (spin_limit != 0): a handful of physical workgroups doing equal work run in
+// lockstep, so the poll after the last arrival would always find its round complete and a tiny limit
+// could not force the timeout path.  With the knob set the workgroup therefore takes its first sample
+// of the top counter AT its last arrival (`last`), before that arrival's own leaf sum — grid_sum2_arrive
+// returns whether it found the round incomplete, and grid_sum2_poll counts it as the first poll.
+__device__ inline bool grid_sum2_arrive(const DopriParams& P, unsigned r, unsigned v, double v0, double v1, bool last) {
+  const unsigned sh = (unsigned)P.leaf_shift, L = 1u << sh;
+  const unsigned x = ((v >> (sh + 3u)) << 3u) | (v & 7u);
+  const unsigned first = ((x >> 3u) << (sh + 3u)) + (x & 7u);
+  const unsigned nx = min(L, ((unsigned)P.nblk_global - first + 7u) >> 3u);
+  double* xs = P.xs + 2 * kDpGroups * (r & 1u);
+  unsigned* abw = dp_abort(P);
+  const int lane = threadIdx.x & 63;
+  int leader = 0, early = 0;
+  if (lane == 0) {
+    const int ab = __hip_atomic_load(abw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
+    dp_st16(&P.slot[2 * v], v0, v1);
+    dp_order();
+    if (!ab)
+      leader = __hip_atomic_fetch_add(dp_cnt(P, x), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == nx * (r + 1u) - 1u;
+    if (!ab && last && P.spin_limit)
+      early = (int)(__hip_atomic_load(dp_top(P, blockIdx.x % kDpTopCopies), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) -
+                    (unsigned)P.n_leaf_local * (r + 1u)) < 0;
+  }
+  leader = __shfl(leader, 0);
+  early = __shfl(early, 0);
+  if (leader) {
+    dp_order();
+    double a0 = 0.0, a1 = 0.0;
+    for (unsigned j = lane; j < nx; j += 64) {
+      double u0, u1;
+      dp_ld16(&P.slot[2 * (first + (j << 3u))], u0, u1);
+      a0 += u0;
+      a1 += u1;
+    }
+    a0 = xor_sum64(a0);
+    a1 = xor_sum64(a1);
+    if (lane == 0) dp_st16(&xs[2 * x], a0, a1);
+    dp_order();
+    if (lane < kDpTopCopies) __hip_atomic_fetch_add(dp_top(P, lane), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  return early != 0;
+}
+__device__ inline bool grid_sum2_poll(const DopriParams& P, unsigned r, bool early, double& s0, double& s1) {
+  const unsigned ngrp = (unsigned)P.n_leaf_local;
+  const double* xs = P.xs + 2 * kDpGroups * (r & 1u);
+  unsigned* abw = dp_abort(P);
+  const int lane = threadIdx.x & 63;
+  int ab = 0;
+  if (lane == 0) {
+    ab = __hip_atomic_load(abw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
+    const unsigned want = ngrp * (r + 1u);
+    unsigned spins = 0;
+    unsigned* top = dp_top(P, blockIdx.x % kDpTopCopies);
+    if (!ab && early && ++spins == P.spin_limit) {   // the sample at the last arrival was the last allowed
+      __hip_atomic_store(abw, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      ab = 1;
+    }
+    while (!ab && (int)(__hip_atomic_load(top, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - want) < 0) {
+      __builtin_amdgcn_s_sleep(1);
+      if ((spins & 15u) == 15u && __hip_atomic_load(abw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
+        ab = 1;
+        break;
+      }
+      if (++spins == (P.spin_limit ? P.spin_limit : kDpSpinLimit)) {
+        __hip_atomic_store(abw, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        ab = 1;
+        break;
+      }
+    }
+    dp_order();
+  }
+  ab = __shfl(ab, 0);
+  double u0 = 0.0, u1 = 0.0;
+  if ((unsigned)lane < ngrp && !ab) dp_ld16(&xs[2 * lane], u0, u1);
   s0 = xor_sum64(u0);
   s1 = xor_sum64(u1);
   return ab != 0;

@@ -465,7 +465,7 @@ def _try_field_resident(func, y0, tp, reversed_, rtol, atol, options):
         xr = D.XRank.get(grp, dev)
         if not xr.ok:   # agreed over the group: every rank takes the host loop
             return None
-    elif B > lib.fetode_integrate_dopri5_max_batch(handle.ref, 0):
+    elif B > _resident_cap(lib, handle, lib.fetode_integrate_dopri5_max_batch(handle.ref, 0)):
         # no resident solver for this shape / batch: decide BEFORE pack_state, which rebinds the
         # layers' prev_x to the fused state buffer (a declined launch would leave them there and
         # skip the first-call re-initialisation of the host loop's first evaluation)
@@ -678,8 +678,8 @@ def _try_field_resident_train(func, y0, tp, reversed_, rtol, atol, options):
     handle = make_handle(field, B, dev)
     if not (lib.fetode_fused_supported(handle.ref) and lib.fetode_fused_backward_supported(handle.ref)):
         return None
-    if B > min(lib.fetode_integrate_dopri5_max_batch(handle.ref, 0),
-               lib.fetode_integrate_dopri5_backward_max_batch(handle.ref)):
+    if B > _resident_cap(lib, handle, min(lib.fetode_integrate_dopri5_max_batch(handle.ref, 0),
+                                          lib.fetode_integrate_dopri5_backward_max_batch(handle.ref))):
         return None
     params = list(field.parameters())
     return _FusedDopri5Fn.apply(field, handle, y0.to(torch.float32).contiguous(), _t_device(tp, dev), float(rtol), float(atol),
@@ -788,6 +788,24 @@ class _EcgDopri5Fn(torch.autograd.Function):
 
 
 _ECG_RESIDENT_TRAIN = os.environ.get("FETODE_ECG_DOPRI5_TAPE", "0") == "1"
+
+
+def set_resident_dopri5_multipass(enabled: bool) -> bool:
+    """Multi-pass mode of the resident LV dopri5 launches (fetode_dopri5_set_multipass; off by default,
+    env FETODE_DOPRI5_MULTIPASS=1): a batch beyond one co-resident grid — inference, the taped training
+    solve and its reverse sweep — runs on a grid of at most that capacity, each workgroup serving
+    several virtual workgroups between two grid sums, instead of falling back to the host-driven
+    loop / host autograd.  The results are bitwise those a one-grid launch of the batch would give.
+    Returns the previous value."""
+    return bool(_lib.load().fetode_dopri5_set_multipass(1 if enabled else 0))
+
+
+def _resident_cap(lib, handle, one_grid_cap):
+    """The largest batch of the resident single-device LV solve: the one-grid cap, or with the
+    multi-pass mode on (and a field that has it) fetode_integrate_dopri5_multipass_max_batch."""
+    if lib.fetode_dopri5_set_multipass(-1):   # a negative argument only queries
+        return max(one_grid_cap, lib.fetode_integrate_dopri5_multipass_max_batch(handle.ref))
+    return one_grid_cap
 
 
 def set_resident_ecg_training(enabled: bool) -> bool:

@@ -102,8 +102,40 @@ int32_t fetode_resident_launch_mode(int32_t mode);
  * grid-reduction / cross-rank spin before it gives up with status 4 (0 = the built-in limits,
  * ~1 s single device, ~16 s across ranks).  A tiny limit forces the timeout path on a healthy
  * grid (tests/test_gpu_dopri5.py: the pre-solve hysteresis state is restored).  Returns the
- * previous value.  Process-wide. */
+ * previous value.  Process-wide.  In a multi-pass launch (below) a workgroup's first poll of a round
+ * is the sample it takes at its last arrival, before that arrival's own leaf sum, while a limit is
+ * set: a few workgroups in lockstep would otherwise never see an incomplete round. */
 uint32_t fetode_dopri5_set_spin_limit(uint32_t polls);
+/* Multi-pass mode of the resident LV dopri5 launches (the [2, 10, 2] KAN / KAN-FET kernels of
+ * fetode_integrate_dopri5, fetode_integrate_dopri5_tape and fetode_integrate_dopri5_backward).
+ * Off (default; env FETODE_DOPRI5_MULTIPASS=1 turns it on): a batch beyond one co-resident grid
+ * is FETODE_EUNSUPPORTED, and every workspace size and *_max_batch is what it always was.  On: such
+ * a batch runs on a grid no larger than the co-resident capacity, each workgroup serving several
+ * "virtual" workgroups (the workgroups a one-grid launch would have used) in turn between two grid
+ * sums and parking what a trajectory carries across a sum in the workspace; the grid sums are
+ * formed over the virtual grid in the one-grid order, so solution, state, tape, attempt log and
+ * gradients are bitwise those of a one-grid launch of that batch.  The batch is then bounded by
+ * memory and fetode_integrate_dopri5_multipass_max_batch; fetode_integrate_dopri5_workspace and
+ * fetode_integrate_dopri5_backward_workspace[_ev] include the parking areas.  A batch that fits one
+ * grid takes the one-grid kernels as before.  The sharded entry points (*_xrank) and the other field
+ * widths are unaffected.  Process-wide; on < 0 only queries; returns the previous value. */
+int fetode_dopri5_set_multipass(int on);
+/* Test knob: at most this many physical workgroups in a multi-pass launch, forward and sweep alike
+ * (a batch whose one-grid launch needs more takes the multi-pass kernels, however small it is).
+ * 0 (default): the occupancy alone.  No effect while multi-pass is off.  Returns the previous value. */
+int64_t fetode_dopri5_set_grid_limit(int64_t workgroups);
+/* The largest batch the multi-pass mode accepts for this field: 2^31 / 14 = 153391689 for the
+ * [2, 10, 2] fields (the sweep addresses a trajectory's tape row of 2 D + H = 14 floats by a 32-bit
+ * element offset; every other offset is 64-bit or smaller), 0 for shapes without the mode (other
+ * widths, an explicit branch_sign).  Independent of the switch. */
+int64_t fetode_integrate_dopri5_multipass_max_batch(const fetode_field_t* field);
+/* Test knob: the shape of the one-grid reverse sweep of the [2, 10, 2] fields
+ * (fetode_integrate_dopri5_backward): 0 (default) chosen by the batch — one trajectory per wave
+ * while that grid fills at most half of its co-resident capacity, else two; 1 / 2 that many
+ * trajectories per wave at every batch (the workspace queries follow).  The two shapes differ in
+ * the association of the parameter-gradient sums only.  The multi-pass sweep always has the shape
+ * of 2.  Any other argument changes nothing (a query); returns the previous value. */
+int fetode_integrate_dopri5_backward_set_shape(int tpw);
 int fetode_abi_version(void);
 
 /* Size in bytes of the packed "plan" (pre-transformed parameters). */
