@@ -34,6 +34,7 @@
 #include <type_traits>
 
 #include "fetode_common.h"
+#include "fetode_dopri_ctl.h"
 
 using namespace fetode;
 
@@ -1030,7 +1031,7 @@ int fetode_integrate_dopri5_backward(const fetode_field_t* f, const void* plan, 
   if (!plan || !t || !opts || !tableau || !grad_solution || !tape || !attempts || !init_rec || !workspace ||
       !status || (f->ferro && !state0 && (init_mask & 3u) != 3u))
     return set_err(FETODE_EINVAL, "dopri5 backward: null pointer");
-  const int base = opts[0] > 0.0 ? 1 : 2;
+  const int base = dopri_base(opts);
   if (n_att < 0 || n_ev != base + 6 * n_att)
     return set_err(FETODE_EINVAL, "dopri5 backward: %d evaluations do not match %d attempts", n_ev, n_att);
   if (fieldn)
@@ -1098,11 +1099,7 @@ int fetode_integrate_dopri5_backward(const fetode_field_t* f, const void* plan, 
   }
   d.rtol = (float)rtol;
   d.atol = (float)atol;
-  d.safety = opts[1];
-  d.ifactor = opts[2];
-  d.dfactor = opts[3];
-  d.min_step = opts[4];
-  d.max_step = opts[5];
+  dopri_step_from_opts(opts, d.step);
   d.n_el = (double)B * f->kan[0].in_features;
   d.gp.bar = bar;
   d.gp.slot = slot;

@@ -637,7 +637,8 @@ struct DopriBwdArgs {
   const double* init_rec;  // {d0, d1, d2, h0, h1}
   float beta[6][6], cerr[7], cmid[7];
   float rtol, atol;
-  double safety, ifactor, dfactor, min_step, max_step, n_el;
+  DopriStep step;  // first_step unused: base says whether it was given
+  double n_el;
   DopriParams gp;       // the grid-sum words and leaf layout (single device)
   int32_t* status;      // 0, or 4 when a grid sum timed out
 };

@@ -8,6 +8,7 @@
 #include <type_traits>
 
 #include "fetode_common.h"
+#include "fetode_dopri_ctl.h"
 
 using namespace fetode;
 

@@ -68,7 +68,7 @@
   if (threadIdx.x == 0) {
     s_ab = 0;
     s_ra = RareArgs{da.att, da.t, a.gsol, a.gy0, da.init_rec, a.B, da.base, da.n_att, da.rtol, da.atol,
-                    da.n_el, da.safety, da.ifactor, da.dfactor, da.min_step, da.max_step};
+                    da.n_el, da.step.safety, da.step.ifactor, da.step.dfactor, da.step.min_step, da.step.max_step};
 #pragma unroll
     for (int q = 0; q < 36; ++q) s_beta[q / 6][q % 6] = da.beta[q / 6][q % 6];
 #pragma unroll
@@ -321,26 +321,11 @@
       const int fe = m >= 0 ? s_ra.base + 6 * m + 5 : 0;
       const int e2 = s_ra.base + 6 * n;
       C.dt32 = ((float)dt);
-      // control: dt_{n+1} = clamp(dt * min(ifactor, max(safety ratio^-1/5, dfac))) (rk_common.
-      // _optimal_step_size, fp64).  The factor the forward took is dt_{n+1} / dt_n from the attempt
-      // log, so no pow here: the middle term was taken unless the factor sits on a bound (or the
-      // clamp did), and its derivative is -factor / (5 ratio).  The last attempt's next dt feeds
-      // nothing (its adjoint is 0).
       const double rr = (double)ratio;
       double rbar = 0.0, dtbb = 0.0;
-      if (n + 1 < s_ra.n_att) {
-        const double dtn1 = s_ra.att[4 * (n + 1) + 1];
-        const bool clamped = (s_ra.min_step > 0.0 && dtn1 == s_ra.min_step) || dtn1 == s_ra.max_step;
-        if (!clamped) {
-          const double fac = dtn1 / dt;
-          dtbb = C.dtbar * fac;
-          if (rr > 0.0) {
-            const double dfac = rr < 1.0 ? 1.0 : s_ra.dfactor;
-            const bool bound = fabs(fac - s_ra.ifactor) <= 1e-12 * s_ra.ifactor || fabs(fac - dfac) <= 1e-12 * dfac;
-            if (!bound) rbar = C.dtbar * dt * (-0.2 * fac / rr);
-          }
-        }
-      }
+      if (n + 1 < s_ra.n_att)
+        dopri_next_dt_adjoint(C.dtbar, dt, s_ra.att[4 * (n + 1) + 1], rr, s_ra.ifactor, s_ra.dfactor, s_ra.min_step,
+                              s_ra.max_step, dtbb, rbar);
       C.dtb_base = dtbb;
       double pd = 0.0, pt = 0.0;
       float dtb32 = 0.f, yb0, yb1;
@@ -369,12 +354,9 @@
         kbv[7] = fbc;
         yb0 = 0.f;
         fab = 0.f;
-        // interp._interp_fit (fetode_fused.hip's op order)
-        const float ym = y + midv, fa = kv[1], fbk = kv[7];
-        const float co1 = C.dt32 * fa;
-        const float co2 = ((C.dt32 * (fbk - 4.0f * fa) - 11.0f * y) - 5.0f * y1) + 16.0f * ym;
-        const float co3 = ((C.dt32 * (5.0f * fa - 3.0f * fbk) + 18.0f * y) + 14.0f * y1) - 32.0f * ym;
-        const float co4 = ((2.0f * C.dt32) * (fbk - fa) - 8.0f * (y1 + y)) + 16.0f * ym;
+        const float fa = kv[1], fbk = kv[7];
+        float co[5];  // the forward's interpolant
+        dopri_fit(co, y, y1, midv, fa, fbk, C.dt32);
         float c0 = 0.f, c1 = 0.f, c2 = 0.f, c3 = 0.f, c4 = 0.f;
         const double t1 = t0 + dt, dlt = t1 - t0;
         for (; C.jj >= 1 && s_ra.t[C.jj] > t0; --C.jj) {  // outputs in (t0, t1]: uniform over the grid
@@ -386,7 +368,7 @@
           c2 += g * x2;
           c3 += g * x3;
           c4 += g * (x3 * x);
-          const float dsdx = co1 + 2.0f * x * co2 + 3.0f * x2 * co3 + 4.0f * x3 * co4;
+          const float dsdx = co[1] + 2.0f * x * co[2] + 3.0f * x2 * co[3] + 4.0f * x3 * co[4];
           const double xb = (double)(g * dsdx);
           pt += xb * (-1.0 / dlt);
           pd += xb * (-(double)x / dlt);
@@ -439,35 +421,13 @@
         E.dtb32 = dtb32;
       }
     } else if (!in_att && ev == 1) {
-      // _select_initial_step (dopri5.py select_initial_step, fp32): dt0 = min(100 h0, h1)
-      const float d0 = (float)s_ra.init_rec[0], d1 = (float)s_ra.init_rec[1], d2 = (float)s_ra.init_rec[2];
-      const float h0 = (float)s_ra.init_rec[3], h1 = (float)s_ra.init_rec[4];
+      // the initial step's adjoint: dt0 back to h0, d1 and the probe's rms
+      const float h0 = (float)s_ra.init_rec[3];
       C.h0f = (h0);
-      const double dtb = C.dtbar;
-      double h1b = 0.0;
-      C.h0b = 0.0;
-      const float a100 = 100.0f * h0, ah1 = fabsf(h1), sh1 = h1 < 0.f ? -1.f : 1.f;
-      if (a100 < ah1) C.h0b = 100.0 * dtb;
-      else if (ah1 < a100) h1b = dtb * sh1;
-      else {
-        C.h0b = 50.0 * dtb;
-        h1b = 0.5 * dtb * sh1;
-      }
-      double d2b = 0.0, d1b_ = 0.0;
-      if (d1 <= 1e-15f && d2 <= 1e-15f) {  // h1 = max(1e-6, h0 1e-3)
-        const float v = h0 * 1e-3f;
-        if (v > 1e-6f) C.h0b += 1e-3 * h1b;
-        else if (v == 1e-6f) C.h0b += 0.5e-3 * h1b;
-      } else {  // h1 = (0.01 / max(d1, d2)) ** (1/5); Python's max keeps d1 on a tie
-        const bool take2 = d2 > d1;
-        const double mx = take2 ? d2 : d1, base = 0.01 / mx;
-        const double mxb = -(h1b * 0.2 * (double)h1 / base) * base / mx;
-        if (take2) d2b += mxb;
-        else d1b_ += mxb;
-      }
-      // d2 = |rms((f1 - f0) / scale) / h0|
-      const double r2 = (double)d2 * h0, r2b = d2b / h0;
-      C.h0b = (C.h0b - d2b * d2 / h0);
+      double h0b, d1b_, r2, r2b;
+      dopri_dt0_adjoint(C.dtbar, (float)s_ra.init_rec[1], (float)s_ra.init_rec[2], h0, (float)s_ra.init_rec[4], h0b, d1b_,
+                        r2, r2b);
+      C.h0b = (h0b);
       C.d1b = (d1b_);
       float f1b = 0.f, f0bp = 0.f, scb = 0.f;
       if (el && r2 > 0.0) {
@@ -485,7 +445,6 @@
         E.scb = scb;
       }
       C.d0b = 0.0;
-      (void)d0;
     } else if (ev == 0) {
       if (s_ra.base == 2) {  // the rest of _select_initial_step: d0 = rms(y0 / scale), d1 = rms(f0 / scale)
         const float d0 = (float)s_ra.init_rec[0], d1 = (float)s_ra.init_rec[1];
@@ -549,11 +508,7 @@
         double S0, S1;
         gsum(el ? (double)(xb * f0) : 0.0, 0.0, S0, S1);
         C.h0b = (C.h0b + S0);
-        const float d0 = (float)s_ra.init_rec[0], d1 = (float)s_ra.init_rec[1];
-        if (!(d0 < 1e-5f || d1 < 1e-5f)) {  // h0 = |0.01 d0 / d1|
-          C.d0b = (C.h0b * 0.01 / d1);
-          C.d1b = (C.d1b - C.h0b * (double)C.h0f / d1);
-        }
+        dopri_h0_adjoint(C.h0b, C.h0f, (float)s_ra.init_rec[0], (float)s_ra.init_rec[1], C.d0b, C.d1b);
       }
     } else {  // evaluation 0: f(y0)
       if (el) {
@@ -586,11 +541,7 @@
             C.tbar = (C.tbar + S1);
           } else {
             C.h0b = (C.h0b + S0);
-            const float d0 = (float)s_ra.init_rec[0], d1 = (float)s_ra.init_rec[1];
-            if (!(d0 < 1e-5f || d1 < 1e-5f)) {  // h0 = |0.01 d0 / d1|
-              C.d0b = (C.h0b * 0.01 / d1);
-              C.d1b = (C.d1b - C.h0b * (double)C.h0f / d1);
-            }
+            dopri_h0_adjoint(C.h0b, C.h0f, (float)s_ra.init_rec[0], (float)s_ra.init_rec[1], C.d0b, C.d1b);
           }
           wsync();
           s_sc0[wid] = C;

@@ -17,6 +17,7 @@
 #include <cstring>
 
 #include "fetode_common.h"
+#include "fetode_dopri_ctl.h"
 #include "fetode_ecg_dev.h"
 
 using namespace fetode;
@@ -250,8 +251,7 @@ struct EcgDopriArgs {
   const double* t;  // (T) strictly increasing
   int T;
   float rtol, atol;
-  double first_step;  // > 0: options["first_step"]; else _select_initial_step
-  double safety, ifactor, dfactor, min_step, max_step;
+  DopriStep step;
   int max_steps;
   DopriTab tab;
   float* sol;         // (T, B, D)
@@ -537,34 +537,22 @@ __device__ __forceinline__ void ecg_dopri5_body(const Args& a) {
   if (real) a.sol[b * D + d] = y;
   float f0 = eval(y);
   double dt;
-  if (a.first_step > 0.0) {
-    dt = a.first_step;
-  } else {  // misc._select_initial_step in fp32 (dopri5.py select_initial_step)
+  if (a.step.first_step > 0.0) {
+    dt = a.step.first_step;
+  } else {
     const float scale = a.atol + a.rtol * fabsf(y);
     double s;
     const float q0 = y / scale, q1 = f0 / scale;
     double s1;
     global_sum2(real ? (double)q0 * q0 : 0.0, real ? (double)q1 * q1 : 0.0, s, s1);
-    const float d0 = fabsf(sqrtf((float)(s / n_el)));
-    const float d1 = fabsf(sqrtf((float)(s1 / n_el)));
-    float h0 = (d0 < 1e-5f || d1 < 1e-5f) ? 1e-6f : (0.01f * d0) / d1;
-    h0 = fabsf(h0);
+    float d0, d1, d2, h1;
+    const float h0 = dopri_h0(s, s1, n_el, d0, d1);
     const float f1 = eval(y + f0 * h0);
     const float q2 = (f1 - f0) / scale;
     global_sum2(real ? (double)q2 * q2 : 0.0, 0.0, s, s1);
-    const float d2 = fabsf(sqrtf((float)(s / n_el)) / h0);  // (status 4: the loop below is skipped)
-    float h1;
-    if (d1 <= 1e-15f && d2 <= 1e-15f) h1 = fmaxf(1e-6f, h0 * 1e-3f);
-    else h1 = (float)pow((double)(0.01f / fmaxf(d1, d2)), (double)0.2f);  // fp64 pow rounded once: host == device
-    dt = (double)fminf(100.0f * h0, fabsf(h1));
+    dt = dopri_dt0(s, n_el, h0, d1, d2, h1);  // (status 4: the loop below is skipped)
     if constexpr (TAPE) {
-      if (blockIdx.x == 0 && tid == 0 && a.init_rec) {
-        a.init_rec[0] = d0;
-        a.init_rec[1] = d1;
-        a.init_rec[2] = d2;
-        a.init_rec[3] = h0;
-        a.init_rec[4] = h1;
-      }
+      if (blockIdx.x == 0 && tid == 0 && a.init_rec) dopri_init_record(a.init_rec, d0, d1, d2, h0, h1);
     }
   }
 
@@ -576,7 +564,7 @@ __device__ __forceinline__ void ecg_dopri5_body(const Args& a) {
     while (next_t > t1s) {
       if (n_steps >= a.max_steps) { status = 3; break; }
       const double t0 = t1s;
-      if (!(t0 + dt > t0)) { status = 2; break; }
+      if (dopri_underflow(t0, dt)) { status = 2; break; }
       const float dt32 = (float)dt;
       const double t1 = t0 + dt;
       // rk_common._runge_kutta_step via fetode_lincomb's op order, accumulated as the stages
@@ -605,23 +593,12 @@ __device__ __forceinline__ void ecg_dopri5_body(const Args& a) {
       global_sum2(real ? (double)qe * qe : 0.0, (real && !__builtin_isfinite(y)) ? 1.0 : 0.0, s, nbad);
       if (status) break;
       if (nbad != 0.0) { status = 1; break; }
-      const float ratio = sqrtf((float)(s / n_el));
-      const bool accept = ratio <= 1.0f;
-      if (blockIdx.x == 0 && tid == 0 && n_att < a.max_att) {
-        double* o = a.att + (int64_t)n_att * 4;
-        o[0] = t0;
-        o[1] = dt;
-        o[2] = (double)ratio;
-        o[3] = accept ? 1.0 : 0.0;
-      }
+      const float ratio = dopri_ratio(s, n_el);
+      const bool accept = dopri_accept(ratio);
+      if (blockIdx.x == 0 && tid == 0) dopri_log_attempt(a.att, n_att, a.max_att, t0, dt, ratio, accept);
       ++n_att;
-      if (accept) {  // interp._interp_fit (fetode_interp_fit's op order)
-        const float ym = y + mid, fa = f0, fb6 = kn;
-        co[4] = ((2.0f * dt32) * (fb6 - fa) - 8.0f * (y1 + y)) + 16.0f * ym;
-        co[3] = ((dt32 * (5.0f * fa - 3.0f * fb6) + 18.0f * y) + 14.0f * y1) - 32.0f * ym;
-        co[2] = ((dt32 * (fb6 - 4.0f * fa) - 11.0f * y) - 5.0f * y1) + 16.0f * ym;
-        co[1] = dt32 * fa;
-        co[0] = y;
+      if (accept) {
+        dopri_fit(co, y, y1, mid, f0, kn, dt32);
         y = y1;
         f0 = kn;
         t0s = t0;
@@ -629,28 +606,11 @@ __device__ __forceinline__ void ecg_dopri5_body(const Args& a) {
       } else {
         t0s = t0;
       }
-      // rk_common._optimal_step_size in fp64 (dopri5.py optimal_step)
-      const double rr = (double)ratio;
-      double nxt;
-      if (rr == 0.0) {
-        nxt = dt * a.ifactor;
-      } else {
-        const double dfac = rr < 1.0 ? 1.0 : a.dfactor;
-        const double factor = __builtin_isnan(rr) ? rr : fmin(a.ifactor, fmax(a.safety / pow(rr, 1.0 / 5.0), dfac));
-        nxt = dt * factor;
-      }
-      dt = __builtin_isnan(nxt) ? nxt : fmin(fmax(nxt, a.min_step), a.max_step);
+      dt = dopri_next_dt(dt, ratio, a.step);
       ++n_steps;
     }
     if (status) break;
-    const float x = (float)((next_t - t0s) / (t1s - t0s));  // interp._interp_evaluate
-    float total = co[0] + x * co[1];
-    float xp = x;
-#pragma unroll
-    for (int j = 2; j < 5; ++j) {
-      xp = xp * x;
-      total = total + xp * co[j];
-    }
+    const float total = dopri_eval(co, (float)((next_t - t0s) / (t1s - t0s)));
     if (real) a.sol[(int64_t)i * BD + b * D + d] = total;
   }
   // module state after the solve: prev_x = the last evaluation's last-row input; branch_state of
@@ -738,13 +698,7 @@ int ecg_dopri5_impl(const fetode_hlogistic_t* layer, const float* wT, const floa
   a.T = T;
   a.rtol = (float)rtol;
   a.atol = (float)atol;
-  a.first_step = opts[0];
-  a.safety = opts[1];
-  a.ifactor = opts[2];
-  a.dfactor = opts[3];
-  a.min_step = opts[4];
-  a.max_step = opts[5];
-  a.max_steps = opts[6] > 2e9 ? 2000000000 : (int)opts[6];
+  a.max_steps = dopri_step_from_opts(opts, a.step);
   memcpy(&a.tab, tableau, sizeof(DopriTab));
   a.sol = solution;
   a.prev_out = prev_out;

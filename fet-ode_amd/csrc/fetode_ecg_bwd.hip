@@ -30,6 +30,7 @@
 #include <cstring>
 
 #include "fetode_common.h"
+#include "fetode_dopri_ctl.h"
 #include "fetode_ecg_dev.h"
 
 using namespace fetode;
@@ -50,7 +51,8 @@ struct EcgBwdArgs {
   const double* t;     // (T) output times
   int T;
   float rtol, atol;
-  double safety, ifactor, dfactor, min_step, max_step, n_el;
+  DopriStep step;  // first_step unused: base says whether it was given
+  double n_el;
   DopriTab tab;
   const float* gsol;   // (T, B, D) d loss / d solution
   const float* tape;   // (n_ev, 2, B, D)
@@ -219,26 +221,11 @@ __global__ __launch_bounds__(kBwdThreads) void ecg_dopri5_bwd_kernel(EcgBwdArgs 
       const int fe = m >= 0 ? base + 6 * m + 5 : 0;
       const int e2 = base + 6 * n;
       dt32 = (float)dt;
-      // control: dt_{n+1} = clamp(dt * min(ifactor, max(safety ratio^-1/5, dfac))) (rk_common.
-      // _optimal_step_size, fp64).  The factor the forward took is dt_{n+1} / dt_n from the attempt
-      // log, so no pow here: the middle term was taken unless the factor sits on a bound (or the
-      // clamp did), and its derivative is -factor / (5 ratio).  The last attempt's next dt feeds
-      // nothing (its adjoint is 0).
       const double rr = (double)ratio;
       double rbar = 0.0, dtbb = 0.0;
-      if (n + 1 < a.n_att) {
-        const double dtn1 = a.att[4 * (n + 1) + 1];
-        const bool clamped = (a.min_step > 0.0 && dtn1 == a.min_step) || dtn1 == a.max_step;
-        if (!clamped) {
-          const double fac = dtn1 / dt;
-          dtbb = dtbar * fac;
-          if (rr > 0.0) {
-            const double dfac = rr < 1.0 ? 1.0 : a.dfactor;
-            const bool bound = fabs(fac - a.ifactor) <= 1e-12 * a.ifactor || fabs(fac - dfac) <= 1e-12 * dfac;
-            if (!bound) rbar = dtbar * dt * (-0.2 * fac / rr);
-          }
-        }
-      }
+      if (n + 1 < a.n_att)
+        dopri_next_dt_adjoint(dtbar, dt, a.att[4 * (n + 1) + 1], rr, a.step.ifactor, a.step.dfactor, a.step.min_step,
+                              a.step.max_step, dtbb, rbar);
       dtb_base = dtbb;
       pd = pt = 0.0;
       dtb32 = 0.f;
@@ -266,12 +253,9 @@ __global__ __launch_bounds__(kBwdThreads) void ecg_dopri5_bwd_kernel(EcgBwdArgs 
         kbv[7] = fbc;
         yb0 = 0.f;
         fab = 0.f;
-        // interp._interp_fit (the forward's op order)
-        const float ym = y + midv, fa = kv[1], fbk = kv[7];
-        const float co1 = dt32 * fa;
-        const float co2 = ((dt32 * (fbk - 4.0f * fa) - 11.0f * y) - 5.0f * y1) + 16.0f * ym;
-        const float co3 = ((dt32 * (5.0f * fa - 3.0f * fbk) + 18.0f * y) + 14.0f * y1) - 32.0f * ym;
-        const float co4 = ((2.0f * dt32) * (fbk - fa) - 8.0f * (y1 + y)) + 16.0f * ym;
+        const float fa = kv[1], fbk = kv[7];
+        float co[5];  // the forward's interpolant
+        dopri_fit(co, y, y1, midv, fa, fbk, dt32);
         float c0 = 0.f, c1 = 0.f, c2 = 0.f, c3 = 0.f, c4 = 0.f;
         const double t1 = t0 + dt, dlt = t1 - t0;
         for (; jj >= 1 && a.t[jj] > t0; --jj) {  // outputs in (t0, t1]: uniform over the grid
@@ -283,7 +267,7 @@ __global__ __launch_bounds__(kBwdThreads) void ecg_dopri5_bwd_kernel(EcgBwdArgs 
           c2 += g * x2;
           c3 += g * x3;
           c4 += g * (x3 * x);
-          const float dsdx = co1 + 2.0f * x * co2 + 3.0f * x2 * co3 + 4.0f * x3 * co4;
+          const float dsdx = co[1] + 2.0f * x * co[2] + 3.0f * x2 * co[3] + 4.0f * x3 * co[4];
           const double xbd = (double)(g * dsdx);
           pt += xbd * (-1.0 / dlt);
           pd += xbd * (-(double)x / dlt);
@@ -418,11 +402,7 @@ __global__ __launch_bounds__(kBwdThreads) void ecg_dopri5_bwd_kernel(EcgBwdArgs 
       double S0, S1;
       gsum(el ? (double)(xb * f0) : 0.0, 0.0, S0, S1);
       h0b = h0b + S0;
-      const float d0 = (float)a.init_rec[0], d1 = (float)a.init_rec[1];
-      if (!(d0 < 1e-5f || d1 < 1e-5f)) {  // h0 = |0.01 d0 / d1|
-        d0b = h0b * 0.01 / d1;
-        d1b = d1b - h0b * (double)h0f / d1;
-      }
+      dopri_h0_adjoint(h0b, h0f, (float)a.init_rec[0], (float)a.init_rec[1], d0b, d1b);
     } else {  // evaluation 0: f(y0)
       if (el) {
         ybc += xb;
@@ -710,7 +690,7 @@ int fetode_ecg_dopri5_backward(const fetode_hlogistic_t* layer, const float* w, 
   rc = check_shape(layer, "ecg dopri5 backward");
   if (rc) return rc;
   const int F = layer->in_dim * layer->num_basis;
-  const int base = opts[0] > 0.0 ? 1 : 2;
+  const int base = dopri_base(opts);
   if (n_att < 0 || (int64_t)n_ev != (int64_t)base + 6 * (int64_t)n_att)
     return set_err(FETODE_EINVAL, "ecg dopri5 backward: %d evaluations do not match %d attempts (expected %lld)", n_ev,
                    n_att, (long long)base + 6 * (long long)n_att);
@@ -735,11 +715,7 @@ int fetode_ecg_dopri5_backward(const fetode_hlogistic_t* layer, const float* w, 
   a.T = T;
   a.rtol = (float)rtol;
   a.atol = (float)atol;
-  a.safety = opts[1];
-  a.ifactor = opts[2];
-  a.dfactor = opts[3];
-  a.min_step = opts[4];
-  a.max_step = opts[5];
+  dopri_step_from_opts(opts, a.step);
   a.n_el = (double)(B * D);
   memcpy(&a.tab, tableau, sizeof(DopriTab));
   a.gsol = grad_solution;

@@ -25,6 +25,7 @@
 #include <cstdlib>
 
 #include "fetode_common.h"
+#include "fetode_dopri_ctl.h"
 #include "fetode_fieldn_plan.h"
 
 using namespace fetode;
@@ -312,7 +313,8 @@ struct FdArgs {
   const double* init_rec;
   float beta[6][6], cerr[7], cmid[7];
   float rtol, atol;
-  double safety, ifactor, dfactor, min_step, max_step, n_el;
+  DopriStep step;  // first_step unused: base says whether it was given
+  double n_el;
   DopriParams gp;
   int32_t* status;
   float *Xc, *Hc;       // planes (n_ev, B, D) / (n_ev, B, H): the layer inputs, for the parameter VJPs
@@ -450,19 +452,9 @@ __global__ __launch_bounds__(64 * kFbWaves) void fieldn_dopri_bwd_kernel(FdArgs 
       C.dt32 = (float)dt;
       const double rr = (double)ratio;
       double rbar = 0.0, dtbb = 0.0;
-      if (n + 1 < da.n_att) {  // rk_common._optimal_step_size's adjoint (the factor from the log)
-        const double dtn1 = att[4 * (n + 1) + 1];
-        const bool clamped = (da.min_step > 0.0 && dtn1 == da.min_step) || dtn1 == da.max_step;
-        if (!clamped) {
-          const double fac = dtn1 / dt;
-          dtbb = C.dtbar * fac;
-          if (rr > 0.0) {
-            const double dfac = rr < 1.0 ? 1.0 : da.dfactor;
-            const bool bound = fabs(fac - da.ifactor) <= 1e-12 * da.ifactor || fabs(fac - dfac) <= 1e-12 * dfac;
-            if (!bound) rbar = C.dtbar * dt * (-0.2 * fac / rr);
-          }
-        }
-      }
+      if (n + 1 < da.n_att)
+        dopri_next_dt_adjoint(C.dtbar, dt, att[4 * (n + 1) + 1], rr, da.step.ifactor, da.step.dfactor, da.step.min_step,
+                              da.step.max_step, dtbb, rbar);
       C.dtb_base = dtbb;
       double pd = 0.0, pt = 0.0;
       float dtb32 = 0.f, yb0, yb1;
@@ -487,11 +479,9 @@ __global__ __launch_bounds__(64 * kFbWaves) void fieldn_dopri_bwd_kernel(FdArgs 
         kbv[7] = fbc;
         yb0 = 0.f;
         fab = 0.f;
-        const float ym = y + midv, fa = kv[1], fbk = kv[7];
-        const float co1 = C.dt32 * fa;
-        const float co2 = ((C.dt32 * (fbk - 4.0f * fa) - 11.0f * y) - 5.0f * y1) + 16.0f * ym;
-        const float co3 = ((C.dt32 * (5.0f * fa - 3.0f * fbk) + 18.0f * y) + 14.0f * y1) - 32.0f * ym;
-        const float co4 = ((2.0f * C.dt32) * (fbk - fa) - 8.0f * (y1 + y)) + 16.0f * ym;
+        const float fa = kv[1], fbk = kv[7];
+        float co[5];  // the forward's interpolant
+        dopri_fit(co, y, y1, midv, fa, fbk, C.dt32);
         float c0 = 0.f, c1 = 0.f, c2 = 0.f, c3 = 0.f, c4 = 0.f;
         const double t1 = t0 + dt, dlt = t1 - t0;
         for (; C.jj >= 1 && da.t[C.jj] > t0; --C.jj) {  // outputs in (t0, t1]
@@ -503,7 +493,7 @@ __global__ __launch_bounds__(64 * kFbWaves) void fieldn_dopri_bwd_kernel(FdArgs 
           c2 += g * x2;
           c3 += g * x3;
           c4 += g * (x3 * x);
-          const float dsdx = co1 + 2.0f * x * co2 + 3.0f * x2 * co3 + 4.0f * x3 * co4;
+          const float dsdx = co[1] + 2.0f * x * co[2] + 3.0f * x2 * co[3] + 4.0f * x3 * co[4];
           const double xb = (double)(g * dsdx);
           pt += xb * (-1.0 / dlt);
           pd += xb * (-(double)x / dlt);
@@ -552,34 +542,13 @@ __global__ __launch_bounds__(64 * kFbWaves) void fieldn_dopri_bwd_kernel(FdArgs 
         E.yb1 = yb1;
         E.dtb32 = dtb32;
       }
-    } else if (!in_att && ev == 1) {  // _select_initial_step (fp32): dt0 = min(100 h0, h1)
-      const float d1 = (float)da.init_rec[1], d2 = (float)da.init_rec[2];
-      const float h0 = (float)da.init_rec[3], h1 = (float)da.init_rec[4];
+    } else if (!in_att && ev == 1) {  // the initial step's adjoint: dt0 back to h0, d1 and the probe's rms
+      const float h0 = (float)da.init_rec[3];
       C.h0f = h0;
-      const double dtb = C.dtbar;
-      double h1b = 0.0;
-      C.h0b = 0.0;
-      const float a100 = 100.0f * h0, ah1 = fabsf(h1), sh1 = h1 < 0.f ? -1.f : 1.f;
-      if (a100 < ah1) C.h0b = 100.0 * dtb;
-      else if (ah1 < a100) h1b = dtb * sh1;
-      else {
-        C.h0b = 50.0 * dtb;
-        h1b = 0.5 * dtb * sh1;
-      }
-      double d2b = 0.0, d1b_ = 0.0;
-      if (d1 <= 1e-15f && d2 <= 1e-15f) {
-        const float v = h0 * 1e-3f;
-        if (v > 1e-6f) C.h0b += 1e-3 * h1b;
-        else if (v == 1e-6f) C.h0b += 0.5e-3 * h1b;
-      } else {  // h1 = (0.01 / max(d1, d2)) ** (1/5); Python's max keeps d1 on a tie
-        const bool take2 = d2 > d1;
-        const double mx = take2 ? d2 : d1, bse = 0.01 / mx;
-        const double mxb = -(h1b * 0.2 * (double)h1 / bse) * bse / mx;
-        if (take2) d2b += mxb;
-        else d1b_ += mxb;
-      }
-      const double r2 = (double)d2 * h0, r2b = d2b / h0;  // d2 = |rms((f1 - f0) / scale) / h0|
-      C.h0b = C.h0b - d2b * d2 / h0;
+      double h0b, d1b_, r2, r2b;
+      dopri_dt0_adjoint(C.dtbar, (float)da.init_rec[1], (float)da.init_rec[2], h0, (float)da.init_rec[4], h0b, d1b_, r2,
+                        r2b);
+      C.h0b = h0b;
       C.d1b = d1b_;
       float f1b = 0.f, f0bp = 0.f, scb = 0.f;
       if (el && r2 > 0.0) {
@@ -652,11 +621,7 @@ __global__ __launch_bounds__(64 * kFbWaves) void fieldn_dopri_bwd_kernel(FdArgs 
       double S0, S1;
       gsum(el ? (double)(xb * f0) : 0.0, 0.0, S0, S1);
       C.h0b = C.h0b + S0;
-      const float d0 = (float)da.init_rec[0], d1 = (float)da.init_rec[1];
-      if (!(d0 < 1e-5f || d1 < 1e-5f)) {  // h0 = |0.01 d0 / d1|
-        C.d0b = C.h0b * 0.01 / d1;
-        C.d1b = C.d1b - C.h0b * (double)C.h0f / d1;
-      }
+      dopri_h0_adjoint(C.h0b, C.h0f, (float)da.init_rec[0], (float)da.init_rec[1], C.d0b, C.d1b);
     } else {  // evaluation 0: f(y0)
       if (el) {
         E.ybc += xb;
@@ -887,7 +852,7 @@ int fetode::fieldn_dopri5_backward(const fetode_field_t* f, const void* plan, in
   d.att = attempts;
   d.n_att = n_att;
   d.n_ev = n_ev;
-  d.base = opts[0] > 0.0 ? 1 : 2;
+  d.base = dopri_base(opts);
   d.t = t;
   d.init_rec = init_rec;
   for (int i = 0; i < 6; ++i)
@@ -898,11 +863,7 @@ int fetode::fieldn_dopri5_backward(const fetode_field_t* f, const void* plan, in
   }
   d.rtol = (float)rtol;
   d.atol = (float)atol;
-  d.safety = opts[1];
-  d.ifactor = opts[2];
-  d.dfactor = opts[3];
-  d.min_step = opts[4];
-  d.max_step = opts[5];
+  dopri_step_from_opts(opts, d.step);
   d.n_el = (double)B * D;
   d.gp.bar = (unsigned*)(ws + w.bar);
   d.gp.slot = (double*)(ws + w.slot);

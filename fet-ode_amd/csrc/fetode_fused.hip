@@ -14,6 +14,7 @@
 #include <type_traits>
 
 #include "fetode_common.h"
+#include "fetode_dopri_ctl.h"
 #include "fetode_fieldn_plan.h"
 #if (defined(FETODE_EXP_NO_GRIDSUM) || defined(FETODE_EXP_NO_EVAL)) && !defined(FETODE_DIAG)
 #error "FETODE_EXP_NO_GRIDSUM / FETODE_EXP_NO_EVAL are diagnostic knobs: build them with make diag"
@@ -796,32 +797,20 @@ __global__ __launch_bounds__(192) void small6_kernel(FusedArgs a) {
       auto sq = [](f2 q) { return (double)q.x * q.x + (double)q.y * q.y; };
       f2 f0 = tape_eval(y);
       double dt;
-      if (P.first_step > 0.0) {
-        dt = P.first_step;
-      } else {  // misc._select_initial_step in fp32
+      if (P.step.first_step > 0.0) {
+        dt = P.step.first_step;
+      } else {
         const f2 scale = splat(P.atol) + splat(P.rtol) * f2{fabsf(y.x), fabsf(y.y)};
         const f2 q0 = y / scale, q1 = f0 / scale;
         double s, s1;
         gsum2(sq(q0), sq(q1), s, s1);
-        const float d0 = fabsf(sqrtf((float)(s / n_el)));
-        const float d1 = fabsf(sqrtf((float)(s1 / n_el)));
-        float h0 = (d0 < 1e-5f || d1 < 1e-5f) ? 1e-6f : (0.01f * d0) / d1;
-        h0 = fabsf(h0);
+        float d0, d1, d2, h1;
+        const float h0 = dopri_h0(s, s1, n_el, d0, d1);
         const f2 f1 = tape_eval(y + f0 * splat(h0));
         const f2 q2 = (f1 - f0) / scale;
         gsum2(sq(q2), 0.0, s, s1);
-        const float d2 = fabsf(sqrtf((float)(s / n_el)) / h0);
-        float h1;
-        if (d1 <= 1e-15f && d2 <= 1e-15f) h1 = fmaxf(1e-6f, h0 * 1e-3f);
-        else h1 = (float)pow((double)(0.01f / fmaxf(d1, d2)), (double)0.2f);
-        dt = (double)fminf(100.0f * h0, fabsf(h1));
-        if (TAPE && blockIdx.x == 0 && tid == 0) {
-          P.init_rec[0] = d0;
-          P.init_rec[1] = d1;
-          P.init_rec[2] = d2;
-          P.init_rec[3] = h0;
-          P.init_rec[4] = h1;
-        }
+        dt = dopri_dt0(s, n_el, h0, d1, d2, h1);
+        if (TAPE && blockIdx.x == 0 && tid == 0) dopri_init_record(P.init_rec, d0, d1, d2, h0, h1);
       }
       f2 co[5] = {y, splat(0.f), splat(0.f), splat(0.f), splat(0.f)};
       double t0s = P.t[0], t1s = P.t[0];
@@ -831,7 +820,7 @@ __global__ __launch_bounds__(192) void small6_kernel(FusedArgs a) {
         while (next_t > t1s) {
           if (n_steps >= P.max_steps) { status = 3; break; }
           const double t0 = t1s;
-          if (!(t0 + dt > t0)) { status = 2; break; }
+          if (dopri_underflow(t0, dt)) { status = 2; break; }
           const float dt32 = (float)dt;
           const double t1 = t0 + dt;
           f2 A[6];
@@ -859,23 +848,12 @@ __global__ __launch_bounds__(192) void small6_kernel(FusedArgs a) {
           gsum2(sq(qe), (__builtin_isfinite(y.x) && __builtin_isfinite(y.y)) ? 0.0 : 1.0, s, nbad);
           if (status) break;
           if (nbad != 0.0) { status = 1; break; }
-          const float ratio = sqrtf((float)(s / n_el));
-          const bool accept = ratio <= 1.0f;
-          if (blockIdx.x == 0 && tid == 0 && n_att < P.max_att) {
-            double* o = P.att + (int64_t)n_att * 4;
-            o[0] = t0;
-            o[1] = dt;
-            o[2] = (double)ratio;
-            o[3] = accept ? 1.0 : 0.0;
-          }
+          const float ratio = dopri_ratio(s, n_el);
+          const bool accept = dopri_accept(ratio);
+          if (blockIdx.x == 0 && tid == 0) dopri_log_attempt(P.att, n_att, P.max_att, t0, dt, ratio, accept);
           ++n_att;
-          if (accept) {  // interp._interp_fit (fused4's op order)
-            const f2 ym = y + mid, fa = f0, fb6 = kn, dtv = splat(dt32);
-            co[4] = ((splat(2.0f * dt32)) * (fb6 - fa) - splat(8.0f) * (y1 + y)) + splat(16.0f) * ym;
-            co[3] = ((dtv * (splat(5.0f) * fa - splat(3.0f) * fb6) + splat(18.0f) * y) + splat(14.0f) * y1) - splat(32.0f) * ym;
-            co[2] = ((dtv * (fb6 - splat(4.0f) * fa) - splat(11.0f) * y) - splat(5.0f) * y1) + splat(16.0f) * ym;
-            co[1] = dtv * fa;
-            co[0] = y;
+          if (accept) {
+            dopri_fit(co, y, y1, mid, f0, kn, dt32);
             y = y1;
             f0 = kn;
             t0s = t0;
@@ -883,28 +861,11 @@ __global__ __launch_bounds__(192) void small6_kernel(FusedArgs a) {
           } else {
             t0s = t0;
           }
-          const double rr_ = (double)ratio;
-          double nxt;
-          if (rr_ == 0.0) {
-            nxt = dt * P.ifactor;
-          } else {
-            const double dfac = rr_ < 1.0 ? 1.0 : P.dfactor;
-            const double factor = __builtin_isnan(rr_) ? rr_ : fmin(P.ifactor, fmax(P.safety / pow(rr_, 1.0 / 5.0), dfac));
-            nxt = dt * factor;
-          }
-          dt = __builtin_isnan(nxt) ? nxt : fmin(fmax(nxt, P.min_step), P.max_step);
+          dt = dopri_next_dt(dt, ratio, P.step);
           ++n_steps;
         }
         if (status) break;
-        const float xq = (float)((next_t - t0s) / (t1s - t0s));
-        f2 total = co[0] + splat(xq) * co[1];
-        float xp = xq;
-#pragma unroll
-        for (int j = 2; j < 5; ++j) {
-          xp = xp * xq;
-          total = total + splat(xp) * co[j];
-        }
-        out_write(i, total);
+        out_write(i, dopri_eval(co, (float)((next_t - t0s) / (t1s - t0s))));
       }
       if (blockIdx.x == 0 && tid == 0) {
         P.stats[0] = nfev;
@@ -1621,33 +1582,21 @@ __global__ __launch_bounds__(DOPRI ? 64 : (LDSP ? 64 * kFnWavesL : 64 * kFnWaves
     float f0 = f(y);
     ++nfev;
     double dt;
-    if (P.first_step > 0.0) {
-      dt = P.first_step;
-    } else {  // misc._select_initial_step in fp32 (dopri5.py select_initial_step)
+    if (P.step.first_step > 0.0) {
+      dt = P.step.first_step;
+    } else {
       const float scale = P.atol + P.rtol * fabsf(y);
       const float q0 = y / scale, q1 = f0 / scale;
       double s0, s1;
       gsum2(real ? (double)q0 * q0 : 0.0, real ? (double)q1 * q1 : 0.0, s0, s1);
-      const float d0 = fabsf(sqrtf((float)(s0 / n_el)));
-      const float d1 = fabsf(sqrtf((float)(s1 / n_el)));
-      float h0 = (d0 < 1e-5f || d1 < 1e-5f) ? 1e-6f : (0.01f * d0) / d1;
-      h0 = fabsf(h0);
+      float d0, d1, d2, h1;
+      const float h0 = dopri_h0(s0, s1, n_el, d0, d1);
       const float f1 = f(y + f0 * h0);
       ++nfev;
       const float q2 = (f1 - f0) / scale;
       gsum2(real ? (double)q2 * q2 : 0.0, 0.0, s0, s1);
-      const float d2 = fabsf(sqrtf((float)(s0 / n_el)) / h0);
-      float h1;
-      if (d1 <= 1e-15f && d2 <= 1e-15f) h1 = fmaxf(1e-6f, h0 * 1e-3f);
-      else h1 = (float)pow((double)(0.01f / fmaxf(d1, d2)), (double)0.2f);  // fp64 pow rounded once
-      dt = (double)fminf(100.0f * h0, fabsf(h1));
-      if (TAPE && blockIdx.x == 0 && threadIdx.x == 0) {
-        P.init_rec[0] = d0;
-        P.init_rec[1] = d1;
-        P.init_rec[2] = d2;
-        P.init_rec[3] = h0;
-        P.init_rec[4] = h1;
-      }
+      dt = dopri_dt0(s0, n_el, h0, d1, d2, h1);
+      if (TAPE && blockIdx.x == 0 && threadIdx.x == 0) dopri_init_record(P.init_rec, d0, d1, d2, h0, h1);
     }
     float co[5] = {y, 0.f, 0.f, 0.f, 0.f};
     double t0s = P.t[0], t1s = P.t[0];
@@ -1657,7 +1606,7 @@ __global__ __launch_bounds__(DOPRI ? 64 : (LDSP ? 64 * kFnWavesL : 64 * kFnWaves
       while (next_t > t1s) {
         if (n_steps >= P.max_steps) { status = 3; break; }
         const double t0 = t1s;
-        if (!(t0 + dt > t0)) { status = 2; break; }
+        if (dopri_underflow(t0, dt)) { status = 2; break; }
         const float dt32 = (float)dt;
         const double t1 = t0 + dt;
         // rk_common._runge_kutta_step in fetode_lincomb's op order, accumulated as the stages
@@ -1682,23 +1631,12 @@ __global__ __launch_bounds__(DOPRI ? 64 : (LDSP ? 64 * kFnWavesL : 64 * kFnWaves
         gsum2(real ? (double)qe * qe : 0.0, (real && !__builtin_isfinite(y)) ? 1.0 : 0.0, sq, nbad);
         if (status) break;
         if (nbad != 0.0) { status = 1; break; }
-        const float ratio = sqrtf((float)(sq / n_el));
-        const bool accept = ratio <= 1.0f;
-        if (blockIdx.x == 0 && threadIdx.x == 0 && n_att < P.max_att) {
-          double* o = P.att + (int64_t)n_att * 4;
-          o[0] = t0;
-          o[1] = dt;
-          o[2] = (double)ratio;
-          o[3] = accept ? 1.0 : 0.0;
-        }
+        const float ratio = dopri_ratio(sq, n_el);
+        const bool accept = dopri_accept(ratio);
+        if (blockIdx.x == 0 && threadIdx.x == 0) dopri_log_attempt(P.att, n_att, P.max_att, t0, dt, ratio, accept);
         ++n_att;
-        if (accept) {  // interp._interp_fit (fetode_interp_fit's op order)
-          const float ym = y + mid, fa = f0, fb6 = kn;
-          co[4] = ((2.0f * dt32) * (fb6 - fa) - 8.0f * (y1 + y)) + 16.0f * ym;
-          co[3] = ((dt32 * (5.0f * fa - 3.0f * fb6) + 18.0f * y) + 14.0f * y1) - 32.0f * ym;
-          co[2] = ((dt32 * (fb6 - 4.0f * fa) - 11.0f * y) - 5.0f * y1) + 16.0f * ym;
-          co[1] = dt32 * fa;
-          co[0] = y;
+        if (accept) {
+          dopri_fit(co, y, y1, mid, f0, kn, dt32);
           y = y1;
           f0 = kn;
           t0s = t0;
@@ -1706,27 +1644,11 @@ __global__ __launch_bounds__(DOPRI ? 64 : (LDSP ? 64 * kFnWavesL : 64 * kFnWaves
         } else {
           t0s = t0;
         }
-        // rk_common._optimal_step_size in fp64 (dopri5.py optimal_step)
-        const double rr = (double)ratio;
-        double nxt;
-        if (rr == 0.0) {
-          nxt = dt * P.ifactor;
-        } else {
-          const double dfac = rr < 1.0 ? 1.0 : P.dfactor;
-          const double factor = __builtin_isnan(rr) ? rr : fmin(P.ifactor, fmax(P.safety / pow(rr, 1.0 / 5.0), dfac));
-          nxt = dt * factor;
-        }
-        dt = __builtin_isnan(nxt) ? nxt : fmin(fmax(nxt, P.min_step), P.max_step);
+        dt = dopri_next_dt(dt, ratio, P.step);
         ++n_steps;
       }
       if (status) break;
-      const float xq = (float)((next_t - t0s) / (t1s - t0s));  // interp._interp_evaluate
-      float total = co[0] + xq * co[1];
-      float xp = xq;
-      for (int j = 2; j < 5; ++j) {
-        xp = xp * xq;
-        total = total + xp * co[j];
-      }
+      const float total = dopri_eval(co, (float)((next_t - t0s) / (t1s - t0s)));
       if (real) a.solution[((int64_t)i * a.B + b) * D + o] = total;
     }
     if (P.xr_world > 1 && blockIdx.x == 0 && threadIdx.x == 0)  // the exchange workgroup may stop
@@ -2085,13 +2007,7 @@ static int dopri5_launch(const fetode_field_t* f, const void* plan, const float*
   P.T = T;
   P.rtol = (float)rtol;
   P.atol = (float)atol;
-  P.first_step = opts[0];
-  P.safety = opts[1];
-  P.ifactor = opts[2];
-  P.dfactor = opts[3];
-  P.min_step = opts[4];
-  P.max_step = opts[5];
-  P.max_steps = opts[6] > 2e9 ? 2000000000 : (int)opts[6];
+  P.max_steps = dopri_step_from_opts(opts, P.step);
   for (int j = 0; j < 7; ++j) {  // tableau = beta (6 x 6, row i = stage i + 1), c_error (7), c_mid (7)
     for (int q = 0; q < 6; ++q) P.stc[j][q] = (j < 6 && j + q < 6) ? tableau[(j + q) * 6 + j] : 0.0f;
     P.stc[j][6] = tableau[36 + j];

@@ -538,7 +538,7 @@
           ++round;
         };
         // pass 0: f(y0)
-        const bool auto_h = !(P.first_step > 0.0);
+        const bool auto_h = !(P.step.first_step > 0.0);
         for (unsigned v = blockIdx.x; v < VG; v += G) {
           bind(v, 0, true);
           const float yv = valid ? a.y0[b * D + row] : 0.f;
@@ -557,14 +557,12 @@
         ++nfev;
         double dt;
         if (!auto_h) {
-          dt = P.first_step;
-        } else {  // misc._select_initial_step in fp32, the probe as a pass of its own
+          dt = P.step.first_step;
+        } else {  // the initial step, the probe as a pass of its own
           double s, s1;
           poll(s, s1);
-          const float d0 = fabsf(sqrtf((float)(s / n_el)));
-          const float d1 = fabsf(sqrtf((float)(s1 / n_el)));
-          float h0 = (d0 < 1e-5f || d1 < 1e-5f) ? 1e-6f : (0.01f * d0) / d1;
-          h0 = fabsf(h0);
+          float d0, d1, d2, h1;
+          const float h0 = dopri_h0(s, s1, n_el, d0, d1);
           for (unsigned v = blockIdx.x; v < VG; v += G) {
             bind(v, 1, false);
             const float yv = *pk(v, 0), f0 = *pk(v, 1);
@@ -577,18 +575,8 @@
           }
           ++nfev;
           poll(s, s1);
-          const float d2 = fabsf(sqrtf((float)(s / n_el)) / h0);
-          float h1;
-          if (d1 <= 1e-15f && d2 <= 1e-15f) h1 = fmaxf(1e-6f, h0 * 1e-3f);
-          else h1 = (float)pow((double)(0.01f / fmaxf(d1, d2)), (double)0.2f);
-          dt = (double)fminf(100.0f * h0, fabsf(h1));
-          if (TAPE && blockIdx.x == 0 && tid == 0) {
-            P.init_rec[0] = d0;
-            P.init_rec[1] = d1;
-            P.init_rec[2] = d2;
-            P.init_rec[3] = h0;
-            P.init_rec[4] = h1;
-          }
+          dt = dopri_dt0(s, n_el, h0, d1, d2, h1);
+          if (TAPE && blockIdx.x == 0 && tid == 0) dopri_init_record(P.init_rec, d0, d1, d2, h0, h1);
         }
         // the last attempt's part still to be done per trajectory: its accept update (pend_acc, with
         // its dt32) and the outputs [o_lo, o_hi) its interpolant over [t0s, t1s] covers
@@ -599,28 +587,13 @@
         auto finish_last = [&](unsigned v, float& y, float& f0) __attribute__((always_inline)) {
           y = *pk(v, 0);
           f0 = *pk(v, 1);
-          if (pend_acc) {  // interp._interp_fit (fetode_interp_fit's op order)
-            const float y1 = *pk(v, 2), kn = *pk(v, 3), mid = *pk(v, 4), dt32 = pend_dt32;
+          if (pend_acc) {
+            const float y1 = *pk(v, 2), kn = *pk(v, 3), mid = *pk(v, 4);
             float co[5];
-            const float ym = y + mid, fa = f0, fb6 = kn;
-            co[4] = ((2.0f * dt32) * (fb6 - fa) - 8.0f * (y1 + y)) + 16.0f * ym;
-            co[3] = ((dt32 * (5.0f * fa - 3.0f * fb6) + 18.0f * y) + 14.0f * y1) - 32.0f * ym;
-            co[2] = ((dt32 * (fb6 - 4.0f * fa) - 11.0f * y) - 5.0f * y1) + 16.0f * ym;
-            co[1] = dt32 * fa;
-            co[0] = y;
+            dopri_fit(co, y, y1, mid, f0, kn, pend_dt32);
             y = y1;
             f0 = kn;
-            for (int j = o_lo; j < o_hi; ++j) {  // interp._interp_evaluate
-              const float xq = (float)((P.t[j] - t0s) / (t1s - t0s));
-              float total = co[0] + xq * co[1];
-              float xp = xq;
-#pragma unroll
-              for (int q2 = 2; q2 < 5; ++q2) {
-                xp = xp * xq;
-                total = total + xp * co[q2];
-              }
-              out_write(j, total);
-            }
+            for (int j = o_lo; j < o_hi; ++j) out_write(j, dopri_eval(co, (float)((P.t[j] - t0s) / (t1s - t0s))));
             *pk(v, 0) = y;
             *pk(v, 1) = f0;
           }
@@ -636,7 +609,7 @@
           if (i >= P.T) break;
           if (n_steps >= P.max_steps) { status = 3; break; }
           const double t0 = t1s;
-          if (!(t0 + dt > t0)) { status = 2; break; }
+          if (dopri_underflow(t0, dt)) { status = 2; break; }
           const float dt32 = (float)dt;
           const double t1 = t0 + dt;
           for (unsigned v = blockIdx.x; v < VG; v += G) {
@@ -679,31 +652,15 @@
           poll(s, nbad);
           if (status) break;
           if (nbad != 0.0) { status = 1; break; }
-          const float ratio = sqrtf((float)(s / n_el));
-          const bool accept = ratio <= 1.0f;
-          if (blockIdx.x == 0 && tid == 0 && n_att < P.max_att) {
-            double* o = P.att + (int64_t)n_att * 4;
-            o[0] = t0;
-            o[1] = dt;
-            o[2] = (double)ratio;
-            o[3] = accept ? 1.0 : 0.0;
-          }
+          const float ratio = dopri_ratio(s, n_el);
+          const bool accept = dopri_accept(ratio);
+          if (blockIdx.x == 0 && tid == 0) dopri_log_attempt(P.att, n_att, P.max_att, t0, dt, ratio, accept);
           ++n_att;
           pend_acc = accept;
           pend_dt32 = dt32;
           t0s = t0;
           if (accept) t1s = t1;
-          // rk_common._optimal_step_size in fp64 (dopri5.py optimal_step)
-          const double rr = (double)ratio;
-          double nxt;
-          if (rr == 0.0) {
-            nxt = dt * P.ifactor;
-          } else {
-            const double dfac = rr < 1.0 ? 1.0 : P.dfactor;
-            const double factor = __builtin_isnan(rr) ? rr : fmin(P.ifactor, fmax(P.safety / pow(rr, 1.0 / 5.0), dfac));
-            nxt = dt * factor;
-          }
-          dt = __builtin_isnan(nxt) ? nxt : fmin(fmax(nxt, P.min_step), P.max_step);
+          dt = dopri_next_dt(dt, ratio, P.step);
           ++n_steps;
         }
         if (pend_acc && o_lo < o_hi)   // the outputs of the last accepted step
@@ -754,34 +711,22 @@
         ktape(f0);
         ++nfev;
         double dt;
-        if (P.first_step > 0.0) {
-          dt = P.first_step;
-        } else {  // misc._select_initial_step in fp32 (dopri5.py select_initial_step)
+        if (P.step.first_step > 0.0) {
+          dt = P.step.first_step;
+        } else {
           const float scale = P.atol + P.rtol * fabsf(y);
           const float q0 = y / scale, q1 = f0 / scale;
           double s, s1;
           gsum2(real ? (double)q0 * q0 : 0.0, real ? (double)q1 * q1 : 0.0, s, s1);
-          const float d0 = fabsf(sqrtf((float)(s / n_el)));
-          const float d1 = fabsf(sqrtf((float)(s1 / n_el)));
-          float h0 = (d0 < 1e-5f || d1 < 1e-5f) ? 1e-6f : (0.01f * d0) / d1;
-          h0 = fabsf(h0);
+          float d0, d1, d2, h1;
+          const float h0 = dopri_h0(s, s1, n_el, d0, d1);
           const float f1 = eval(y + f0 * h0);
           ktape(f1);
           ++nfev;
           const float q2 = (f1 - f0) / scale;
           gsum2(real ? (double)q2 * q2 : 0.0, 0.0, s, s1);
-          const float d2 = fabsf(sqrtf((float)(s / n_el)) / h0);
-          float h1;
-          if (d1 <= 1e-15f && d2 <= 1e-15f) h1 = fmaxf(1e-6f, h0 * 1e-3f);
-          else h1 = (float)pow((double)(0.01f / fmaxf(d1, d2)), (double)0.2f);  // fp64 pow rounded once: host == device
-          dt = (double)fminf(100.0f * h0, fabsf(h1));
-          if (TAPE && blockIdx.x == 0 && tid == 0) {
-            P.init_rec[0] = d0;
-            P.init_rec[1] = d1;
-            P.init_rec[2] = d2;
-            P.init_rec[3] = h0;
-            P.init_rec[4] = h1;
-          }
+          dt = dopri_dt0(s, n_el, h0, d1, d2, h1);
+          if (TAPE && blockIdx.x == 0 && tid == 0) dopri_init_record(P.init_rec, d0, d1, d2, h0, h1);
         }
         float co[5] = {y, 0.f, 0.f, 0.f, 0.f};
         double t0s = P.t[0], t1s = P.t[0];
@@ -791,7 +736,7 @@
           while (next_t > t1s) {
             if (n_steps >= P.max_steps) { status = 3; break; }
             const double t0 = t1s;
-            if (!(t0 + dt > t0)) { status = 2; break; }
+            if (dopri_underflow(t0, dt)) { status = 2; break; }
             const float dt32 = (float)dt;
             const double t1 = t0 + dt;
             // rk_common._runge_kutta_step in fetode_lincomb's op order, accumulated as the stages
@@ -827,23 +772,12 @@
             STAMP(1);
             if (status) break;
             if (nbad != 0.0) { status = 1; break; }
-            const float ratio = sqrtf((float)(s / n_el));
-            const bool accept = ratio <= 1.0f;
-            if (blockIdx.x == 0 && tid == 0 && n_att < P.max_att) {
-              double* o = P.att + (int64_t)n_att * 4;
-              o[0] = t0;
-              o[1] = dt;
-              o[2] = (double)ratio;
-              o[3] = accept ? 1.0 : 0.0;
-            }
+            const float ratio = dopri_ratio(s, n_el);
+            const bool accept = dopri_accept(ratio);
+            if (blockIdx.x == 0 && tid == 0) dopri_log_attempt(P.att, n_att, P.max_att, t0, dt, ratio, accept);
             ++n_att;
-            if (accept) {  // interp._interp_fit (fetode_interp_fit's op order)
-              const float ym = y + mid, fa = f0, fb6 = kn;
-              co[4] = ((2.0f * dt32) * (fb6 - fa) - 8.0f * (y1 + y)) + 16.0f * ym;
-              co[3] = ((dt32 * (5.0f * fa - 3.0f * fb6) + 18.0f * y) + 14.0f * y1) - 32.0f * ym;
-              co[2] = ((dt32 * (fb6 - 4.0f * fa) - 11.0f * y) - 5.0f * y1) + 16.0f * ym;
-              co[1] = dt32 * fa;
-              co[0] = y;
+            if (accept) {
+              dopri_fit(co, y, y1, mid, f0, kn, dt32);
               y = y1;
               f0 = kn;
               t0s = t0;
@@ -851,30 +785,12 @@
             } else {
               t0s = t0;
             }
-            // rk_common._optimal_step_size in fp64 (dopri5.py optimal_step)
-            const double rr = (double)ratio;
-            double nxt;
-            if (rr == 0.0) {
-              nxt = dt * P.ifactor;
-            } else {
-              const double dfac = rr < 1.0 ? 1.0 : P.dfactor;
-              const double factor = __builtin_isnan(rr) ? rr : fmin(P.ifactor, fmax(P.safety / pow(rr, 1.0 / 5.0), dfac));
-              nxt = dt * factor;
-            }
-            dt = __builtin_isnan(nxt) ? nxt : fmin(fmax(nxt, P.min_step), P.max_step);
+            dt = dopri_next_dt(dt, ratio, P.step);
             ++n_steps;
             STAMP(7);
           }
           if (status) break;
-          const float xq = (float)((next_t - t0s) / (t1s - t0s));  // interp._interp_evaluate
-          float total = co[0] + xq * co[1];
-          float xp = xq;
-#pragma unroll
-          for (int j = 2; j < 5; ++j) {
-            xp = xp * xq;
-            total = total + xp * co[j];
-          }
-          out_write(i, total);
+          out_write(i, dopri_eval(co, (float)((next_t - t0s) / (t1s - t0s))));
         }
         if (P.xr_world > 1 && blockIdx.x == 0 && tid == 0)   // the exchange workgroup may stop
           __hip_atomic_store(dp_fin(P), round + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

@@ -1,16 +1,16 @@
-// fetode_gridsum.h — the device-resident dopri5 solvers' control parameters and their grid-wide
+// fetode_gridsum.h — the device-resident dopri5 solvers' launch parameters and their grid-wide
 // fixed-order fp64 reduction (shared by the forward solve, fetode_fused.hip, and its reverse
-// sweep, fetode_bwd.hip).  Device code only; included inside each file's anonymous namespace.
+// sweep, fetode_bwd.hip).  Device code only; included inside each file's anonymous namespace,
+// after fetode_dopri_ctl.h, which holds the step-control arithmetic itself.
 #pragma once
 // Device-resident dopri5 (torchdiffeq Dopri5Solver, the default method of every reference odeint
-// without `method`, train_kanfet_node_predprey.py:252): the control arithmetic of the host-driven
-// path (fet-ode_amd/dopri5.py _Dopri5 with fetode_lincomb / fetode_scaled_rms / fetode_interp_*).
+// without `method`, train_kanfet_node_predprey.py:252).
 struct DopriParams {
   int32_t on;
   const double* t;  // (T) output times, fp64, strictly increasing
   int32_t T;
   float rtol, atol;
-  double first_step, safety, ifactor, dfactor, min_step, max_step;
+  DopriStep step;  // fetode_dopri_ctl.h
   int32_t max_steps;
   // tableau in fp32 (RKAdaptiveStepsizeODESolver casts it to y0's dtype), by stage column j:
   // stc[j][q] = beta[j + q][j] (q < 6, 0 past the tableau), stc[j][6] = c_error[j], stc[j][7] = c_mid[j]

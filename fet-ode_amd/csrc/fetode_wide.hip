@@ -30,6 +30,7 @@
 #include <cstdlib>
 
 #include "fetode_common.h"
+#include "fetode_dopri_ctl.h"
 
 using namespace fetode;
 
@@ -1279,7 +1280,7 @@ struct WideDopriArgs {
   const double* t;
   int T;
   float rtol, atol;
-  double first_step, safety, ifactor, dfactor, min_step, max_step;
+  DopriStep step;
   int max_steps;
   float stc[7][8];  // tableau columns (DopriParams.stc)
   unsigned* bar;
@@ -1529,7 +1530,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4))) v
     a.sol[i] = y;
   });
   if (tid == 0) {
-    ctl.dt = a.first_step;
+    ctl.dt = a.step.first_step;
     ctl.t0 = ctl.t1 = 0.0;
     ctl.t0s = ctl.t1s = a.t[0];
     ctl.h0 = ctl.d1 = ctl.dt32 = 0.f;
@@ -1592,7 +1593,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4))) v
       for (int q = 0; q < 8; ++q) c[q] = ctl.cc[q];
       const int S1 = a.S1;
       // norm terms: per layer-1 tile (wide_tile_partial) when this evaluation ends in a reduction
-      const bool red = (kind == kCmbF0 && !(a.first_step > 0.0)) || kind == kCmbF1 || (kind == kCmbStage && stg == 5);
+      const bool red = (kind == kCmbF0 && !(a.step.first_step > 0.0)) || kind == kCmbF1 || (kind == kCmbStage && stg == 5);
       double acc0 = 0.0, acc1 = 0.0;
       auto elem = [&](int64_t i) {
         float k = a.ks[i];
@@ -1651,7 +1652,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4))) v
     }
     // ---- the decision (thread 0) ----
     const int kind = ctl.kind, stg = ctl.stg;
-    const bool reduce = !(kind == kCmbF0 && a.first_step > 0.0) && !(kind == kCmbStage && stg < 5);
+    const bool reduce = !(kind == kCmbF0 && a.step.first_step > 0.0) && !(kind == kCmbStage && stg < 5);
     double s0 = 0.0, s1 = 0.0;
     if (reduce && wide_norm(a, nround, s0, s1)) {
       status = 4;
@@ -1668,21 +1669,15 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4))) v
       if (kind == kCmbStage && stg < 5) {
         ctl.stg = stg + 1;
         ctl.next = kNextNone;  // the combine already wrote the next stage input
-      } else if (kind == kCmbF0 && !(a.first_step > 0.0)) {  // misc._select_initial_step in fp32
-        const float d0 = fabsf(sqrtf((float)(s0 / n_el)));
-        const float d1 = fabsf(sqrtf((float)(s1 / n_el)));
-        float h0 = (d0 < 1e-5f || d1 < 1e-5f) ? 1e-6f : (0.01f * d0) / d1;
-        ctl.h0 = fabsf(h0);
+      } else if (kind == kCmbF0 && !(a.step.first_step > 0.0)) {  // the initial step: h0, then the probe
+        float d0, d1;
+        ctl.h0 = dopri_h0(s0, s1, n_el, d0, d1);
         ctl.d1 = d1;
         ctl.kind = kCmbF1;
         ctl.next = kNextProbe;
       } else if (kind == kCmbF1) {
-        const float h0 = ctl.h0, d1 = ctl.d1;
-        const float d2 = fabsf(sqrtf((float)(s0 / n_el)) / h0);
-        float h1;
-        if (d1 <= 1e-15f && d2 <= 1e-15f) h1 = fmaxf(1e-6f, h0 * 1e-3f);
-        else h1 = (float)pow((double)(0.01f / fmaxf(d1, d2)), (double)0.2f);  // fp64 pow rounded once: host == device
-        ctl.dt = (double)fminf(100.0f * h0, fabsf(h1));
+        float d2, h1;
+        ctl.dt = dopri_dt0(s0, n_el, ctl.h0, ctl.d1, d2, h1);
         sched = true;
       } else if (kind == kCmbF0) {  // first_step given
         sched = true;
@@ -1690,16 +1685,9 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4))) v
         if (s1 != 0.0) {
           ctl.status = 1;
         } else {
-          const float ratio = sqrtf((float)(s0 / n_el));
-          const bool accept = ratio <= 1.0f;
-          const double dt = ctl.dt;
-          if (blockIdx.x == 0 && ctl.n_att < a.max_att) {
-            double* o = a.att + (int64_t)ctl.n_att * 4;
-            o[0] = ctl.t0;
-            o[1] = dt;
-            o[2] = (double)ratio;
-            o[3] = accept ? 1.0 : 0.0;
-          }
+          const float ratio = dopri_ratio(s0, n_el);
+          const bool accept = dopri_accept(ratio);
+          if (blockIdx.x == 0) dopri_log_attempt(a.att, ctl.n_att, a.max_att, ctl.t0, ctl.dt, ratio, accept);
           ++ctl.n_att;
           if (accept) {
             ctl.fit = 1;
@@ -1709,16 +1697,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4))) v
           } else {
             ctl.t0s = ctl.t0;
           }
-          const double rr = (double)ratio;
-          double nxt;
-          if (rr == 0.0) {
-            nxt = dt * a.ifactor;
-          } else {
-            const double dfac = rr < 1.0 ? 1.0 : a.dfactor;
-            const double factor = __builtin_isnan(rr) ? rr : fmin(a.ifactor, fmax(a.safety / pow(rr, 1.0 / 5.0), dfac));
-            nxt = dt * factor;
-          }
-          ctl.dt = __builtin_isnan(nxt) ? nxt : fmin(fmax(nxt, a.min_step), a.max_step);
+          ctl.dt = dopri_next_dt(ctl.dt, ratio, a.step);
           ++ctl.n_steps;
           sched = true;
         }
@@ -1738,7 +1717,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4))) v
           ctl.status = 3;
         } else {
           const double t0 = ctl.t1s, dt = ctl.dt;
-          if (!(t0 + dt > t0)) {
+          if (dopri_underflow(t0, dt)) {
             ctl.status = 2;
           } else {
             ctl.t0 = t0;
@@ -1760,17 +1739,14 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4))) v
     }
     __syncthreads();
     // ---- the decision's element passes (owner threads only: no hand-off) ----
-    if (ctl.fit) {  // interp._interp_fit (fetode_interp_fit's op order); y <- y1, f0 <- k7
+    if (ctl.fit) {  // the accepted step's interpolant; y <- y1, f0 <- k7
       const float dtc = ctl.fit_dt32;
       for_owned([&](int64_t i) {
-        const float y = es[kEY * BD + i], y1 = es[kEY1 * BD + i];
-        const float fa = es[kEF0 * BD + i], fb = es[kEKl * BD + i];
-        const float ym = y + es[kEMid * BD + i];
-        es[(kECo + 4) * BD + i] = ((2.0f * dtc) * (fb - fa) - 8.0f * (y1 + y)) + 16.0f * ym;
-        es[(kECo + 3) * BD + i] = ((dtc * (5.0f * fa - 3.0f * fb) + 18.0f * y) + 14.0f * y1) - 32.0f * ym;
-        es[(kECo + 2) * BD + i] = ((dtc * (fb - 4.0f * fa) - 11.0f * y) - 5.0f * y1) + 16.0f * ym;
-        es[(kECo + 1) * BD + i] = dtc * fa;
-        es[kECo * BD + i] = y;
+        const float y1 = es[kEY1 * BD + i], fb = es[kEKl * BD + i];
+        float co[5];
+        dopri_fit(co, es[kEY * BD + i], y1, es[kEMid * BD + i], es[kEF0 * BD + i], fb, dtc);
+#pragma unroll
+        for (int q = 0; q < 5; ++q) es[(kECo + q) * BD + i] = co[q];
         es[kEY * BD + i] = y1;
         es[kEF0 * BD + i] = fb;
       });
@@ -1779,14 +1755,10 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4))) v
       const float xq = (float)((a.t[j] - ctl.t0s) / (ctl.t1s - ctl.t0s));
       float* const so = a.sol + (int64_t)j * BD;
       for_owned([&](int64_t i) {
-        float total = es[kECo * BD + i] + xq * es[(kECo + 1) * BD + i];
-        float xp = xq;
+        float co[5];
 #pragma unroll
-        for (int q = 2; q < 5; ++q) {
-          xp = xp * xq;
-          total = total + xp * es[(kECo + q) * BD + i];
-        }
-        so[i] = total;
+        for (int q = 0; q < 5; ++q) co[q] = es[(kECo + q) * BD + i];
+        so[i] = dopri_eval(co, xq);
       });
     }
     if (ctl.status >= 0) {
@@ -2164,13 +2136,7 @@ int wide_dopri5_launch(const fetode_kanlinear_t* kan0, const fetode_ferro_t* fer
   a.T = T;
   a.rtol = (float)rtol;
   a.atol = (float)atol;
-  a.first_step = opts[0];
-  a.safety = opts[1];
-  a.ifactor = opts[2];
-  a.dfactor = opts[3];
-  a.min_step = opts[4];
-  a.max_step = opts[5];
-  a.max_steps = opts[6] > 2e9 ? 2000000000 : (int)opts[6];
+  a.max_steps = dopri_step_from_opts(opts, a.step);
   for (int j = 0; j < 7; ++j) {  // tableau = beta (6 x 6, row i = stage i + 1), c_error (7), c_mid (7)
     for (int q = 0; q < 6; ++q) a.stc[j][q] = (j < 6 && j + q < 6) ? tableau[(j + q) * 6 + j] : 0.0f;
     a.stc[j][6] = tableau[36 + j];

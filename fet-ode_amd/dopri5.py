@@ -249,6 +249,23 @@ _TABLEAU = np.concatenate([np.concatenate([b, np.zeros(6 - len(b), np.float32)])
 _RESIDENT_OPTS = {"first_step", "safety", "ifactor", "dfactor", "min_step", "max_step", "max_num_steps"}
 
 
+def _scalar_request(y0, reversed_, rtol, atol, options) -> bool:
+    """What every resident solver takes: forward in time, a (B, D) state, scalar tolerances and
+    only the scalar step-control options."""
+    return (not reversed_ and y0.dim() == 2 and not (set(options) - _RESIDENT_OPTS)
+            and isinstance(rtol, (int, float)) and isinstance(atol, (int, float)))
+
+
+def _ecg_shape_ok(func, y0) -> bool:
+    """The ECG field the resident kernels are built for: the sigmoid mixer, the state as wide as
+    the basis input (<= 64) and as the head, no noise, at most 3072 trajectories."""
+    import torch.nn as nn
+    basis = func.feat.basis
+    B, D = y0.shape
+    return (isinstance(func.feat.act, nn.Sigmoid) and D == basis.in_dim and D <= 64 and B <= 3072
+            and func.proj.out_features == D and not basis.use_noise)
+
+
 def _raise_status(status: int, timeout_msg: str, restore=None):
     """torchdiffeq's assertions from a resident solver's status word.  Status 4 (a grid barrier
     timed out: the workgroups were not co-resident) runs ``restore`` first, which puts the
@@ -367,17 +384,12 @@ def _try_ecg_resident(func, y0, tp, reversed_, rtol, atol, options):
     """The whole solve in one launch when `func` is the ECG field (No_MLP_KANODEFunc with the
     sigmoid mixer), nothing needs gradients, and the options are the scalar ones."""
     from .ecg import No_MLP_KANODEFunc
-    import torch.nn as nn
-    if not isinstance(func, No_MLP_KANODEFunc) or reversed_ or y0.dim() != 2:
+    if not isinstance(func, No_MLP_KANODEFunc) or not _scalar_request(y0, reversed_, rtol, atol, options):
         return None
-    if not isinstance(func.feat.act, nn.Sigmoid) or set(options) - _RESIDENT_OPTS:
-        return None
-    if not (isinstance(rtol, (int, float)) and isinstance(atol, (int, float))):
+    if not _ecg_shape_ok(func, y0):
         return None
     basis = func.feat.basis
     B, D = y0.shape
-    if D != basis.in_dim or D > 64 or B > 3072 or func.proj.out_features != D or basis.use_noise:
-        return None
     if torch.is_grad_enabled() and (y0.requires_grad or any(p.requires_grad for p in func.parameters())):
         return None
     lib = _lib.load()
@@ -395,23 +407,14 @@ def _try_ecg_resident(func, y0, tp, reversed_, rtol, atol, options):
     prev = basis._prev_for(dev)
     prev0 = prev.clone()   # the timeout path restores it (the kernel rewrites prev_x in place)
     yc = _lib.f32c(y0)
-    tkey = (dev, tuple(tp.tolist()))   # tp is the host copy odeint made; uploads once per grid
-    t_dev = _T_DEV.get(tkey)
-    if t_dev is None:
-        if len(_T_DEV) > 64:
-            _T_DEV.clear()
-        t_dev = _T_DEV[tkey] = tp.to(torch.float64).to(dev)
+    t_dev = _t_device(tp, dev)
     T = t_dev.numel()
     sol = torch.empty(T, B, D, device=dev, dtype=torch.float32)
     branch = torch.empty(B, basis.in_dim, basis.num_basis, device=dev, dtype=torch.float32)
     ws = torch.empty(max(1, lib.fetode_ecg_dopri5_workspace(B) // 4), device=dev, dtype=torch.float32)
     stats = torch.empty(3, device=dev, dtype=torch.int32)   # the kernel writes all three
     att = torch.empty(_MAX_TRACE, 4, device=dev, dtype=torch.float64)
-    fs = options.get("first_step")
-    opts = np.array([float(fs) if fs is not None else 0.0, float(options.get("safety", 0.9)),
-                     float(options.get("ifactor", 10.0)), float(options.get("dfactor", 0.2)),
-                     float(options.get("min_step", 0.0)), float(options.get("max_step", math.inf)),
-                     float(options.get("max_num_steps", 2 ** 31 - 1))], dtype=np.float64)
+    opts = _opts_array(options)
     rc = lib.fetode_ecg_dopri5(
         _lib.ctypes.byref(d), wT.data_ptr(), _lib.ptr(bias), D, prev.data_ptr(), yc.data_ptr(), B, t_dev.data_ptr(),
         T, float(rtol), float(atol), opts.ctypes.data_as(_lib.ctypes.POINTER(_lib.ctypes.c_double)),
@@ -441,9 +444,7 @@ def _try_field_resident(func, y0, tp, reversed_, rtol, atol, options):
     field = fused_field(func)
     options = dict(options)
     group = options.pop("norm_group", None)
-    if field is None or reversed_ or y0.dim() != 2 or set(options) - _RESIDENT_OPTS:
-        return None
-    if not (isinstance(rtol, (int, float)) and isinstance(atol, (int, float))):
+    if field is None or not _scalar_request(y0, reversed_, rtol, atol, options):
         return None
     if torch.is_grad_enabled() and (y0.requires_grad or any(p.requires_grad for p in field.parameters())):
         return None
@@ -474,22 +475,13 @@ def _try_field_resident(func, y0, tp, reversed_, rtol, atol, options):
     state, mask = pack_state(field, B, dev)
     state0 = None if state is None else state.clone()   # for the timeout path
     yc = _lib.f32c(y0)
-    tkey = (dev, tuple(tp.tolist()))
-    t_dev = _T_DEV.get(tkey)
-    if t_dev is None:
-        if len(_T_DEV) > 64:
-            _T_DEV.clear()
-        t_dev = _T_DEV[tkey] = tp.to(torch.float64).to(dev)
+    t_dev = _t_device(tp, dev)
     T = t_dev.numel()
     sol = torch.empty(T, B, y0.shape[1], device=dev, dtype=torch.float32)
     ws = torch.empty(max(1, lib.fetode_integrate_dopri5_workspace(B) // 4), device=dev, dtype=torch.float32)
     stats = torch.empty(3, device=dev, dtype=torch.int32)
     att = torch.empty(_MAX_TRACE, 4, device=dev, dtype=torch.float64)
-    fs = options.get("first_step")
-    opts = np.array([float(fs) if fs is not None else 0.0, float(options.get("safety", 0.9)),
-                     float(options.get("ifactor", 10.0)), float(options.get("dfactor", 0.2)),
-                     float(options.get("min_step", 0.0)), float(options.get("max_step", math.inf)),
-                     float(options.get("max_num_steps", 2 ** 31 - 1))], dtype=np.float64)
+    opts = _opts_array(options)
     optp = opts.ctypes.data_as(_lib.ctypes.POINTER(_lib.ctypes.c_double))
     tabp = _TABLEAU.ctypes.data_as(_lib.ctypes.POINTER(_lib.ctypes.c_float))
     if xr is not None:
@@ -523,7 +515,7 @@ def _opts_array(options):
 
 
 def _t_device(tp, dev):
-    tkey = (dev, tuple(tp.tolist()))
+    tkey = (dev, tuple(tp.tolist()))   # tp is the host copy odeint made; uploads once per grid
     t_dev = _T_DEV.get(tkey)
     if t_dev is None:
         if len(_T_DEV) > 64:
@@ -668,9 +660,7 @@ def _try_field_resident_train(func, y0, tp, reversed_, rtol, atol, options):
     from .autograd_ops import make_handle
     from .odeint import fused_field
     field = fused_field(func)
-    if field is None or reversed_ or y0.dim() != 2 or set(options) - _RESIDENT_OPTS:
-        return None
-    if not (isinstance(rtol, (int, float)) and isinstance(atol, (int, float))):
+    if field is None or not _scalar_request(y0, reversed_, rtol, atol, options):
         return None
     lib = _lib.load()
     dev = y0.device
@@ -822,18 +812,11 @@ def _try_ecg_resident_train(func, y0, tp, reversed_, rtol, atol, options):
     something needs gradients, the solve is forward in time, the options and tolerances are the
     scalar ones and the batch fits both resident grids; None otherwise (the caller's host path)."""
     from .ecg import No_MLP_KANODEFunc
-    import torch.nn as nn
-    if not isinstance(func, No_MLP_KANODEFunc) or reversed_ or y0.dim() != 2:
-        return None
-    if not isinstance(func.feat.act, nn.Sigmoid) or set(options) - _RESIDENT_OPTS:
-        return None
-    if not (isinstance(rtol, (int, float)) and isinstance(atol, (int, float))):
+    if not isinstance(func, No_MLP_KANODEFunc) or not _scalar_request(y0, reversed_, rtol, atol, options):
         return None
     basis = func.feat.basis
     B, D = y0.shape
-    if D != basis.in_dim or D > 64 or B > 3072 or func.proj.out_features != D or basis.use_noise or B <= 0:
-        return None
-    if basis.in_dim * basis.num_basis > 768:
+    if not _ecg_shape_ok(func, y0) or B <= 0 or basis.in_dim * basis.num_basis > 768:
         return None
     lib = _lib.load()
     keep = []
@@ -861,11 +844,9 @@ def _try_wide_resident(func, y0, tp, reversed_, rtol, atol, options):
     field = fused_field(func)
     options = dict(options)
     group = options.pop("norm_group", None)
-    if field is None or reversed_ or y0.dim() != 2 or set(options) - _RESIDENT_OPTS:
+    if field is None or not _scalar_request(y0, reversed_, rtol, atol, options):
         return None
     if not getattr(field, "has_ferro", False):
-        return None
-    if not (isinstance(rtol, (int, float)) and isinstance(atol, (int, float))):
         return None
     layers = field_layers(field)
     if len(layers) != 2 or any(f is None or f._bsign is not None or f.use_noise for _, f in layers):
@@ -927,22 +908,13 @@ def _try_wide_resident(func, y0, tp, reversed_, rtol, atol, options):
     snap = [(p, p.clone()) for re, p in ((re0, p0), (re1, p1)) if not re]   # for the timeout path
     st0 = torch.empty(B, D, device=dev, dtype=torch.float32) if re0 else p0   # prev_x after the solve
     st1 = torch.empty(B, H, device=dev, dtype=torch.float32) if re1 else p1
-    tkey = (dev, tuple(tp.tolist()))
-    t_dev = _T_DEV.get(tkey)
-    if t_dev is None:
-        if len(_T_DEV) > 64:
-            _T_DEV.clear()
-        t_dev = _T_DEV[tkey] = tp.to(torch.float64).to(dev)
+    t_dev = _t_device(tp, dev)
     T = t_dev.numel()
     sol = torch.empty(T, B, D, device=dev, dtype=torch.float32)
     ws = torch.empty(max(1, ws_bytes // 4), device=dev, dtype=torch.float32)
     stats = torch.empty(3, device=dev, dtype=torch.int32)
     att = torch.empty(_MAX_TRACE, 4, device=dev, dtype=torch.float64)
-    fs = options.get("first_step")
-    opts = np.array([float(fs) if fs is not None else 0.0, float(options.get("safety", 0.9)),
-                     float(options.get("ifactor", 10.0)), float(options.get("dfactor", 0.2)),
-                     float(options.get("min_step", 0.0)), float(options.get("max_step", math.inf)),
-                     float(options.get("max_num_steps", 2 ** 31 - 1))], dtype=np.float64)
+    opts = _opts_array(options)
     by = _lib.ctypes.byref
     optp = opts.ctypes.data_as(_lib.ctypes.POINTER(_lib.ctypes.c_double))
     tabp = _TABLEAU.ctypes.data_as(_lib.ctypes.POINTER(_lib.ctypes.c_float))
