@@ -101,6 +101,7 @@ SIGNATURES = {
     "fetode_abi_version": (ctypes.c_int, []),
     "fetode_resident_launch_mode": (ctypes.c_int32, [ctypes.c_int32]),
     "fetode_plan_bytes": (ctypes.c_int64, [ctypes.POINTER(FieldDesc)]),
+    "fetode_plan_image_bytes": (ctypes.c_int64, [ctypes.POINTER(FieldDesc)]),
     "fetode_plan_build": (ctypes.c_int, [ctypes.POINTER(FieldDesc), _vp, _vp]),
     "fetode_state_width": (ctypes.c_int32, [ctypes.POINTER(FieldDesc)]),
     "fetode_fused_supported": (ctypes.c_int, [ctypes.POINTER(FieldDesc)]),
@@ -294,7 +295,7 @@ def load() -> ctypes.CDLL:
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
-    if lib.fetode_abi_version() != 2:
+    if lib.fetode_abi_version() != 3:
         raise FetodeError("libfetode ABI version mismatch")
     _lib = lib
     return lib

@@ -56,6 +56,7 @@ def build_plan(owner, handle: _lib.FieldHandle, device) -> torch.Tensor:
     nbytes = lib.fetode_plan_bytes(handle.ref)
     if nbytes < 0:
         _lib.check(_lib.FETODE_EINVAL, "fetode_plan_bytes")
+    nbytes += lib.fetode_plan_image_bytes(handle.ref)   # the fused kernels' lane-ordered image, if any
     n = max(1, nbytes // 4)
     plan = getattr(owner, "_fetode_plan", None)
     # a plan a pending backward still reads (pin_plan) is never rebuilt in place: the rebuild gets a

@@ -49,6 +49,12 @@ struct LayerPlan {
 
 void layer_plan(const fetode_kanlinear_t& kl, const fetode_ferro_t* fl, int64_t base, LayerPlan* p);
 int validate_field(const fetode_field_t* f);
+// The lane-ordered image block of fields with a specialised fused kernel (fetode_fused4_image.h,
+// fetode_fused.hip): its size in floats (0: no fused kernel for the field, no block), and its build
+// from the classic sections already enqueued on `stream`; img: the block's float offset in the plan
+// (the last layer's `end`).
+int64_t fused_image_floats(const fetode_field_t* f);
+int fused_image_build(const fetode_field_t* f, float* plan, int64_t img, void* stream);
 
 // depth-2 fields of other widths served by fieldn_kernel (fetode_fused.hip), and their reverse
 // sweep (fetode_fieldn_bwd.hip): arguments and workspace as fetode_integrate_fixed_backward

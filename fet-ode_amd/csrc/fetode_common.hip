@@ -320,6 +320,11 @@ int64_t fetode_plan_bytes(const fetode_field_t* f) {
   return base * (int64_t)sizeof(float);
 }
 
+int64_t fetode_plan_image_bytes(const fetode_field_t* f) {
+  if (validate_field(f) != FETODE_OK) return -1;
+  return fused_image_floats(f) * (int64_t)sizeof(float);   // after the last layer's `end` (16-byte aligned)
+}
+
 int fetode_plan_build(const fetode_field_t* f, void* plan, void* stream) {
   int rc = validate_field(f);
   if (rc) return rc;
@@ -350,7 +355,7 @@ int fetode_plan_build(const fetode_field_t* f, void* plan, void* stream) {
                        (float*)plan);
     LAUNCH_CHECK();
   }
-  return FETODE_OK;
+  return fused_image_build(f, (float*)plan, base, stream);
 }
 
 }  // extern "C"

@@ -16,6 +16,7 @@
 #include "fetode_common.h"
 #include "fetode_dopri_ctl.h"
 #include "fetode_fieldn_plan.h"
+#include "fetode_fused4_image.h"
 #if (defined(FETODE_EXP_NO_GRIDSUM) || defined(FETODE_EXP_NO_EVAL)) && !defined(FETODE_DIAG)
 #error "FETODE_EXP_NO_GRIDSUM / FETODE_EXP_NO_EVAL are diagnostic knobs: build them with make diag"
 #endif
@@ -37,6 +38,9 @@ __device__ __forceinline__ unsigned long long stamp_now() {
 #define STAMP_DECL            \
   unsigned long long st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}; \
   unsigned long long st_last = stamp_now();
+// the prologue (kernel entry to "tables staged") into slot 4, fused4 body only
+#define STAMP_ENTRY const unsigned long long st_entry = stamp_now();
+#define STAMP_PROLOGUE() st_acc[4] = st_last - st_entry
 #define STAMP(p)                                  \
   do {                                            \
     const unsigned long long st_t = stamp_now();  \
@@ -50,6 +54,8 @@ __device__ __forceinline__ unsigned long long stamp_now() {
   } while (0)
 #else
 #define STAMP_DECL
+#define STAMP_ENTRY
+#define STAMP_PROLOGUE()
 #define STAMP(p)
 #define STAMP_FLUSH()
 #endif
@@ -199,6 +205,7 @@ struct FusedArgs {
   float* eval_out;
   float factor_limit;   // kFactorLimit (FETODE_FACTOR_LIMIT=-1 disables the factored gate: diagnostics)
   DopriParams dp;       // dp.on: the whole dopri5 solve in this launch (fetode_integrate_dopri5)
+  int64_t img;          // the lane-ordered image block of the plan (fetode_fused4_image.h), in floats
 };
 
 // integer version (knot counts)
@@ -297,18 +304,6 @@ __device__ __forceinline__ float v4_single(f2 ew, f2 xp, float ep, float k2, flo
   const float th = ffma(rcp(ex2(z) + 1.0f), -2.0f, 1.0f);
   return ffma(cp, th, acc);
 }
-
-// Ferro element split of one layer's output over a lane group: NPAIR element pairs (i, k), (i, k+1)
-// over `lanes` lanes.  When the remainder of pairs is at most half a round, the full rounds stay
-// pairs (NPL per lane) and the leftover pairs' elements go one per lane (NSL = 1: a single-element
-// round costs about half a pair round); otherwise one more pair round (NSL = 0).
-template <int NPAIR, int LANES>
-struct FerroSplit {
-  static constexpr int REM = NPAIR % LANES;
-  static constexpr bool SPLIT = REM > 0 && 2 * REM <= LANES;
-  static constexpr int NPL = SPLIT ? NPAIR / LANES : (NPAIR + LANES - 1) / LANES;
-  static constexpr int NSL = SPLIT ? 1 : 0;
-};
 
 // the edge sum of one lane: NPL Ferro pairs (+ NSL single elements), FPL feature weights, and
 // (spl) the spline edge of input `si` (sp_o = the layer's LDS cubic table at output o, kr = the
@@ -1256,6 +1251,19 @@ __global__ __launch_bounds__(128 * TPB) void v8_kernel(FusedArgs a) {
 }
 
 
+// The plan's image block: one thread per float gathers its source from the classic sections the
+// plan build just wrote (same stream), or stores its pad (the map: fetode_fused4_image.h).
+constexpr int kImgBlock = 256;
+template <int H, int K, int NB, int NG>
+__global__ __launch_bounds__(kImgBlock) void fused_image_kernel(LayerPlan P0, LayerPlan P1, float* __restrict__ plan,
+                                                                int64_t img) {
+  using BLK = Fused4Block<H, K, NB, NG>;
+  const int w = blockIdx.x * kImgBlock + threadIdx.x;
+  if (w >= BLK::NF) return;
+  const ImgSrc s = BLK::src(P0, P1, w);
+  plan[img + w] = s.src ? plan[s.ofs] : s.pad;
+}
+
 typedef void (*fused_fn)(FusedArgs);
 struct FusedEntry {
   int in0, h, out, K, NB, NG;
@@ -1273,6 +1281,8 @@ struct FusedEntry {
   fused_fn rk4_v8x2;  // the same, two trajectories per four-wave workgroup
   fused_fn fn_tape, fn_rk4_tape, fn_rk4_1_tape;  // v4 / v7 recording the fixed-grid training tape
   fused_fn dopri_mp, dopri_mp_tape;  // the multi-pass resident dopri5 driver (fused4_mp_kernel)
+  int img_floats;                    // the plan's image block (fetode_fused4_image.h)
+  void (*img_fn)(LayerPlan, LayerPlan, float*, int64_t);
 };
 const FusedEntry kFused[] = {
     // LV KAN-FET [2,10,2], K=10 (train_kanfet_node_predprey.py:146)
@@ -1283,7 +1293,8 @@ const FusedEntry kFused[] = {
      small6_kernel<true, true, false, true>, fused4_kernel<10, 10, 10, 12, true, true, false, false, 1>,
      v8_kernel<true, 1>, v8_kernel<true, 2>, fused4_kernel<10, 10, 10, 12, true, false, false, true>,
      fused4_kernel<10, 10, 10, 12, true, true, false, true>, fused4_kernel<10, 10, 10, 12, true, true, false, true, 1>,
-     fused4_mp_kernel<10, 10, 10, 12, true, false>, fused4_mp_kernel<10, 10, 10, 12, true, true>},
+     fused4_mp_kernel<10, 10, 10, 12, true, false>, fused4_mp_kernel<10, 10, 10, 12, true, true>,
+     Fused4Block<10, 10, 10, 12>::NF, fused_image_kernel<10, 10, 10, 12>},
     // LV KAN [2,10,2] (predator_prey.py:101)
     {2, 10, 2, 1, 10, 12, false, fused4_kernel<10, 2, 10, 12, false, false>, fused4_kernel<10, 2, 10, 12, false, true>,
      small6_kernel<false, false>, small6_kernel<false, true>, fused4_kernel<10, 2, 10, 12, false, false, true>,
@@ -1292,7 +1303,8 @@ const FusedEntry kFused[] = {
      small6_kernel<false, true, false, true>, fused4_kernel<10, 2, 10, 12, false, true, false, false, 1>,
      v8_kernel<false, 1>, v8_kernel<false, 2>, fused4_kernel<10, 2, 10, 12, false, false, false, true>,
      fused4_kernel<10, 2, 10, 12, false, true, false, true>, fused4_kernel<10, 2, 10, 12, false, true, false, true, 1>,
-     fused4_mp_kernel<10, 2, 10, 12, false, false>, fused4_mp_kernel<10, 2, 10, 12, false, true>},
+     fused4_mp_kernel<10, 2, 10, 12, false, false>, fused4_mp_kernel<10, 2, 10, 12, false, true>,
+     Fused4Block<10, 0, 10, 12>::NF, fused_image_kernel<10, 0, 10, 12>},
 };
 
 // Batches up to kSmallMax take v6 (one trajectory per 3-wave workgroup, latency-bound chain split
@@ -1755,6 +1767,7 @@ int launch_fused(const fetode_field_t* f, FusedArgs& a, void* stream) {
   }
   layer_plan(f->kan[0], f->ferro ? &f->ferro[0] : nullptr, 0, &a.P0);
   layer_plan(f->kan[1], f->ferro ? &f->ferro[1] : nullptr, a.P0.end, &a.P1);
+  a.img = a.P1.end;
   static const float limit = [] {
     const char* e = getenv("FETODE_FACTOR_LIMIT");
     return e ? (float)atof(e) : kFactorLimit;
@@ -1782,6 +1795,25 @@ int launch_fused(const fetode_field_t* f, FusedArgs& a, void* stream) {
 }  // namespace
 
 bool fetode::fieldn_shape_supported(const fetode_field_t* f) { return find_fused(f) == nullptr && fieldn_supported(f); }
+
+int64_t fetode::fused_image_floats(const fetode_field_t* f) {
+  const FusedEntry* e = find_fused(f);
+  return e ? e->img_floats : 0;
+}
+
+int fetode::fused_image_build(const fetode_field_t* f, float* plan, int64_t img, void* stream) {
+  const FusedEntry* e = find_fused(f);
+  if (!e) return FETODE_OK;
+  LayerPlan P0, P1;
+  layer_plan(f->kan[0], f->ferro ? &f->ferro[0] : nullptr, 0, &P0);
+  layer_plan(f->kan[1], f->ferro ? &f->ferro[1] : nullptr, P0.end, &P1);
+  if (img != P1.end) return set_err(FETODE_EINVAL, "plan image: offset %lld != end of the layer sections %lld",
+                                    (long long)img, (long long)P1.end);
+  hipLaunchKernelGGL(e->img_fn, dim3(nblk(e->img_floats, kImgBlock)), dim3(kImgBlock), 0, (hipStream_t)stream, P0, P1,
+                     plan, img);
+  LAUNCH_CHECK();
+  return FETODE_OK;
+}
 
 extern "C" {
 
@@ -2065,6 +2097,7 @@ static int dopri5_launch(const fetode_field_t* f, const void* plan, const float*
   P.n_leaf_global = (int32_t)nleaves(P.nblk_global, P.leaf_shift);
   layer_plan(f->kan[0], f->ferro ? &f->ferro[0] : nullptr, 0, &a.P0);
   layer_plan(f->kan[1], f->ferro ? &f->ferro[1] : nullptr, a.P0.end, &a.P1);
+  a.img = a.P1.end;
   a.factor_limit = kFactorLimit;
   hipStream_t s = (hipStream_t)stream;
   HIP_CHECK_RET(hipMemsetAsync(workspace, 0, sizeof(unsigned) * kDpBarWords, s));

@@ -35,20 +35,44 @@
       return;
     }
   }
+  STAMP_ENTRY
   constexpr int KT = (NG + 2) / 3;                   // knots per group lane
   static_assert(3 * KT >= NG, "knots per group lane");
-  // edge cubic tables by interval, one row of NI + 1 float4 per edge padded to SPR: at a pitch of 12
-  // float4 the rows of units 4 apart (layer 1) / of the same parity (layer 0) start on the same
-  // 16-byte slot of the bank row and the lanes' interval reads collide (35 % of the kernel's LDS
-  // cycles were conflicts, profiles/r06_lds_bench_nores.txt)
-  constexpr int SPR = NI + 2, SPE = (NI + 1) * 4;
-  constexpr int SPT0 = H * D * SPR * 4, SPT1 = D * H * SPR * 4;
-
-  __shared__ __attribute__((aligned(16))) float s_sp0[SPT0];
-  __shared__ __attribute__((aligned(16))) float s_sp1[SPT1];
-  __shared__ __attribute__((aligned(8))) f2 s_kr0[D * (NI + 1)], s_kr1[H * SPR];
-  __shared__ float s_c0[H], s_c1[D];
+  // The parameters arrive in the plan's image block (fetode_fused4_image.h: the one definition of
+  // this kernel's lane map): the LDS tables as the bytes of `s_tab`, this lane's constants as IMG::NV4
+  // float4 slots.  Every load of the prologue is issued before the first wait.
+  using BLK = Fused4Block<H, K, NB, NG>;
+  using TAB = typename BLK::TAB;
+  using IMG = Fused4Lanes<H, K, NB, NG, NLG>;
+  static_assert(IMG::NPL0 == NPL0 && IMG::NSL0 == NSL0 && IMG::NPL1 == NPL1 && IMG::NSL1 == NSL1 &&
+                    IMG::FPL0 == FPL0 && IMG::RF1 == RF1 && IMG::KT == KT,
+                "the lane image and the kernel share one lane map");
+  constexpr int SPR = TAB::SPR;
+  // (the cubic tables' row pitch SPR and the members' order: Fused4Tables)
+  struct __attribute__((aligned(16))) Tables {
+    float sp0[TAB::SPT0], sp1[TAB::SPT1];
+    f2 kr0[TAB::KR0], kr1[TAB::KR1];
+    float c0[H], c1[D];
+    float pad[TAB::NF - TAB::O_END > 0 ? TAB::NF - TAB::O_END : 1];
+  };
+  static_assert(offsetof(Tables, sp1) == 4 * TAB::O_SP1 && offsetof(Tables, kr0) == 4 * TAB::O_KR0 &&
+                    offsetof(Tables, kr1) == 4 * TAB::O_KR1 && offsetof(Tables, c0) == 4 * TAB::O_C0 &&
+                    offsetof(Tables, c1) == 4 * TAB::O_C1,
+                "the LDS image is this struct byte for byte");
+  __shared__ Tables s_tab;
+  auto& s_sp0 = s_tab.sp0;
+  auto& s_sp1 = s_tab.sp1;
+  auto& s_kr0 = s_tab.kr0;
+  auto& s_kr1 = s_tab.kr1;
+  auto& s_c0 = s_tab.c0;
+  auto& s_c1 = s_tab.c1;
   __shared__ __attribute__((aligned(16))) V4Lds<D, FLEN0> s_L0[TPW];
+  // the step / output schedule is staged through LDS in chunks: per-step global loads in the
+  // loop would wait (vmcnt) behind the solution stores of the previous step.  One chunk holds the
+  // reference's 35-point grid; its loads belong to the prologue's burst.
+  constexpr int SCH = 64;
+  __shared__ float s_dt[SCH], s_hh[SCH], s_h6[SCH], s_oslope[SCH];
+  __shared__ int s_ostep[SCH], s_omode[SCH];
 
   const int tid = threadIdx.x;
   const int hh = tid >> 5;                                   // half-wave
@@ -58,29 +82,67 @@
   bool valid = b < a.B;
   V4Lds<D, FLEN0>& L0 = s_L0[g];
 
-  for (int i = tid; i < H * D * SPE; i += 64) s_sp0[(i / SPE) * SPR * 4 + i % SPE] = a.plan[a.P0.sp + i];
-  for (int i = tid; i < D * H * SPE; i += 64) s_sp1[(i / SPE) * SPR * 4 + i % SPE] = a.plan[a.P1.sp + i];
-  for (int i = tid; i < D * (NI + 1); i += 64) {
-    const int in = i / (NI + 1), m = i % (NI + 1);
-    s_kr0[i] = m < NI ? f2{a.plan[a.P0.knots + in * NG + m], a.plan[a.P0.rh + in * NI + m]} : f2{0.f, 0.f};
-  }
-  for (int i = tid; i < H * (NI + 1); i += 64) {
-    const int in = i / (NI + 1), m = i % (NI + 1);
-    s_kr1[in * SPR + m] = m < NI ? f2{a.plan[a.P1.knots + in * NG + m], a.plan[a.P1.rh + in * NI + m]} : f2{0.f, 0.f};
-  }
-  for (int i = tid; i < H; i += 64) s_c0[i] = a.plan[a.P0.fconst + i];
-  for (int i = tid; i < D; i += 64) s_c1[i] = a.plan[a.P1.fconst + i];
-  for (int i = lane; i < FLEN0; i += 32) L0.F[i] = 0.f;  // pads stay zero (finite x zero weight)
-
-  const bool fact = FERRO && a.plan[a.P0.flag] <= a.factor_limit && a.plan[a.P1.flag] <= a.factor_limit;
-  const float l2 = FETODE_LOG2E;
-
   // ---- layer-0 edge lane: output o0 = 5 row + q/3, part cc0 ----
   const int q = c1;
   const int o0 = row * 5 + q / 3, cc0 = q % 3;
   const bool act0 = q < 15 && o0 < H;
   const int o0c = act0 ? o0 : 0;
   const int gl = TPW == 2 ? cc0 : cc0 + 3 * hh;              // lane within the hidden unit's group
+  const bool x_silu = c1 == J_SILU, x_gate = FERRO && c1 == J_GATE, x_exp = FERRO && c1 == J_EXP;
+  const bool x_x = c1 == J_X;
+
+  // ---- the prologue's loads, all issued before the first wait ----
+  // the first schedule chunk: step tid and output 1 + tid on lane tid (selected when stored)
+  const bool sched0 = !DOPRI && !a.single_eval;
+  const bool sc_st = sched0 && a.n_steps > 0, sc_out = sched0 && a.T > 1, sc_in = 1 + tid < a.T;
+  float sc_dt = 0.f, sc_hh = 0.f, sc_h6 = 0.f, sc_osl = 0.f;
+  int sc_os = -1, sc_om = 1;
+  if (sc_st) {
+    const int i = tid < a.n_steps ? tid : a.n_steps - 1;
+    sc_dt = a.step_coef[4 * i + 0];
+    sc_hh = a.step_coef[4 * i + 1];
+    sc_h6 = a.step_coef[4 * i + 2];
+  }
+  if (sc_out) {
+    const int j = sc_in ? 1 + tid : a.T - 1;
+    sc_os = a.out_step[j];
+    sc_om = a.out_mode[j];
+    sc_osl = a.out_slope[j];
+  }
+  // hysteresis state: prev_x of input `row` on the layer-0 gate lane, of input o0 on every lane
+  // of its group (each forms the gate itself) (ferro_class.py:409); per-layer contiguous blocks
+  // (include/fetode.h)
+  float prev0 = 0.f, prev1 = 0.f;
+  if (FERRO && valid) {
+    if (x_gate) prev0 = a.state[b * D + row];
+    if (act0) prev1 = a.state[a.B * D + b * H + o0];
+  }
+  float y = valid ? a.y0[b * D + row] : 0.f;   // state dim `row`, replicated over the row
+  typedef float v4f __attribute__((ext_vector_type(4)));
+  const v4f* __restrict__ img4 = reinterpret_cast<const v4f*>(a.plan + a.img);
+  constexpr int NT4 = TAB::NF / 4, NTR = (NT4 + 63) / 64;    // the tables' float4s, rounds of 64 lanes
+  v4f tv[NTR], li[IMG::NV4];
+#pragma unroll
+  for (int j = 0; j < NTR; ++j) {
+    const int i = tid + 64 * j;   // (the last round's spare lanes re-read the last float4)
+    tv[j] = img4[BLK::OFS_LDS / 4 + ((j + 1) * 64 <= NT4 || i < NT4 ? i : NT4 - 1)];
+  }
+  {
+    const v4f* lp = img4 + (TPW == 2 ? BLK::OFS_L3 : BLK::OFS_L6) / 4 + (TPW == 2 ? lane : tid);
+#pragma unroll
+    for (int j = 0; j < IMG::NV4; ++j) li[j] = lp[j * IMG::L];
+  }
+  // float slot s of this lane's image (s: a constant after unrolling)
+  auto LI = [&](int s) __attribute__((always_inline)) -> float {
+    return li[s / 4][s % 4];
+  };
+  for (int i = lane; i < FLEN0; i += 32) L0.F[i] = 0.f;  // pads stay zero (finite x zero weight)
+
+  const bool fact = FERRO && a.plan[a.img] <= a.factor_limit && a.plan[a.img + 1] <= a.factor_limit;   // the guard words
+  const float l2 = FETODE_LOG2E;
+
+  // the Ferro constants: exp(gs Ec) when the gate is factored (pads: gec = 0, k2 = kE = cp = 0)
+  auto gexp = [&](float gec) __attribute__((always_inline)) -> float { return fact ? ex2(gec) : gec; };
   f2 ep0[NPL0 > 0 ? NPL0 : 1], k20[NPL0 > 0 ? NPL0 : 1], kE0[NPL0 > 0 ? NPL0 : 1], cp0[NPL0 > 0 ? NPL0 : 1];
   int gi0[NPL0 > 0 ? NPL0 : 1];
 #pragma unroll
@@ -90,20 +152,11 @@
     int i = ok ? P / KP : 0;
     asm volatile("" : "+v"(i));  // keep in a VGPR (no per-evaluation rematerialisation)
     gi0[r] = i;
-    float t[4][2];
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const int64_t idx = (int64_t)o0c * (D * K) + i * K + (ok ? (P % KP) * 2 + h : 0);
-      const float gec = ok ? a.plan[a.P0.fe_GEc + idx] : 0.f;
-      t[0][h] = fact ? ex2(gec) : gec;
-      t[1][h] = ok ? a.plan[a.P0.fe_k2 + idx] : 0.f;
-      t[2][h] = ok ? a.plan[a.P0.fe_k2Ec + idx] : 0.f;
-      t[3][h] = ok ? a.plan[a.P0.fe_CPs2 + idx] : 0.f;
-    }
-    ep0[r] = f2{t[0][0], t[0][1]};
-    k20[r] = f2{t[1][0], t[1][1]};
-    kE0[r] = f2{t[2][0], t[2][1]};
-    cp0[r] = f2{t[3][0], t[3][1]};
+    const int s = IMG::S_P0 + 8 * r;
+    ep0[r] = f2{gexp(LI(s)), gexp(LI(s + 1))};
+    k20[r] = f2{LI(s + 2), LI(s + 3)};
+    kE0[r] = f2{LI(s + 4), LI(s + 5)};
+    cp0[r] = f2{LI(s + 6), LI(s + 7)};
   }
   // layer-0 single: leftover element q = cc0 of pair NPL0 * 3 + q / 2
   int gs0 = 0;
@@ -111,59 +164,35 @@
   if constexpr (NSL0 > 0) {
     const int Pl = NPL0 * NLG + gl / 2;
     const bool ok = act0 && gl < 2 * FS0::REM;
-    const int i = ok ? Pl / KP : 0;
-    const int64_t idx = (int64_t)o0c * (D * K) + i * K + (ok ? (Pl % KP) * 2 + gl % 2 : 0);
-    const float gec = ok ? a.plan[a.P0.fe_GEc + idx] : 0.f;
-    es0 = fact ? ex2(gec) : gec;
-    k2s0 = ok ? a.plan[a.P0.fe_k2 + idx] : 0.f;
-    kEs0 = ok ? a.plan[a.P0.fe_k2Ec + idx] : 0.f;
-    cps0 = ok ? a.plan[a.P0.fe_CPs2 + idx] : 0.f;
-    gs0 = i;
+    es0 = gexp(LI(IMG::S_S0));
+    k2s0 = LI(IMG::S_S0 + 1);
+    kEs0 = LI(IMG::S_S0 + 2);
+    cps0 = LI(IMG::S_S0 + 3);
+    gs0 = ok ? Pl / KP : 0;
     asm volatile("" : "+v"(gs0));
   }
   f2 fw0[FPL0 / 2];
 #pragma unroll
-  for (int f = 0; f < FPL0; f += 2) {
-    float w[2];
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const int qq = gl * FPL0 + f + h, i = qq / NFP, ff = qq % NFP;
-      w[h] = (act0 && i < D && ff < NFL) ? a.plan[a.P0.kw + (int64_t)o0c * (D * NFL) + i * NFL + ff] : 0.f;
-    }
-    fw0[f / 2] = f2{w[0], w[1]};
-  }
+  for (int f = 0; f < FPL0; f += 2) fw0[f / 2] = f2{LI(IMG::S_FW0 + f), LI(IMG::S_FW0 + f + 1)};
   // ---- layer-1 (v7): hidden input o0 on its group; lane gl owns k = gl + NLG r ----
   // pair r: elements (o0, d = 0, k) and (o0, d = 1, k): .x feeds output 0, .y output 1
+  // (padding: ep = 1 (fact) / 0, k = 0: th = 0, cp = 0)
   f2 ep1[NPL1 > 0 ? NPL1 : 1], k21[NPL1 > 0 ? NPL1 : 1], kE1[NPL1 > 0 ? NPL1 : 1], cp1[NPL1 > 0 ? NPL1 : 1];
 #pragma unroll
   for (int r = 0; r < NPL1; ++r) {
-    const int k = gl + NLG * r;
-    const bool ok = act0 && k < K;
-    float t[4][2];
-#pragma unroll
-    for (int d = 0; d < 2; ++d) {
-      const int64_t idx = (int64_t)d * (H * K) + o0c * K + (ok ? k : 0);
-      const float gec = ok ? a.plan[a.P1.fe_GEc + idx] : 0.f;
-      t[0][d] = fact ? ex2(gec) : gec;   // padding: ep = 1 (fact) / 0, k = 0: th = 0, cp = 0
-      t[1][d] = ok ? a.plan[a.P1.fe_k2 + idx] : 0.f;
-      t[2][d] = ok ? a.plan[a.P1.fe_k2Ec + idx] : 0.f;
-      t[3][d] = ok ? a.plan[a.P1.fe_CPs2 + idx] : 0.f;
-    }
-    ep1[r] = f2{t[0][0], t[0][1]};
-    k21[r] = f2{t[1][0], t[1][1]};
-    kE1[r] = f2{t[2][0], t[2][1]};
-    cp1[r] = f2{t[3][0], t[3][1]};
+    const int s = IMG::S_P1 + 8 * r;
+    ep1[r] = f2{gexp(LI(s)), gexp(LI(s + 1))};
+    k21[r] = f2{LI(s + 2), LI(s + 3)};
+    kE1[r] = f2{LI(s + 4), LI(s + 5)};
+    cp1[r] = f2{LI(s + 6), LI(s + 7)};
   }
   // the single left over when K % 3 == 1: element (o0, d = cc0, K - 1) on lanes cc0 = 0, 1
   float es1 = 0.f, k2s1 = 0.f, kEs1 = 0.f, cps1 = 0.f;
   if constexpr (NSL1 > 0) {
-    const bool ok = act0 && cc0 < D;
-    const int64_t idx = (int64_t)(ok ? cc0 : 0) * (H * K) + o0c * K + (K - 1);
-    const float gec = ok ? a.plan[a.P1.fe_GEc + idx] : 0.f;
-    es1 = fact ? ex2(gec) : gec;
-    k2s1 = ok ? a.plan[a.P1.fe_k2 + idx] : 0.f;
-    kEs1 = ok ? a.plan[a.P1.fe_k2Ec + idx] : 0.f;
-    cps1 = ok ? a.plan[a.P1.fe_CPs2 + idx] : 0.f;
+    es1 = gexp(LI(IMG::S_S1));
+    k2s1 = LI(IMG::S_S1 + 1);
+    kEs1 = LI(IMG::S_S1 + 2);
+    cps1 = LI(IMG::S_S1 + 3);
   }
   // lane cc0 = d < 2 also owns the spline edge (o0 -> d): the single / spline value goes to output d
   const f2 dsel1 = f2{(act0 && gl == 0) ? 1.f : 0.f, (act0 && gl == 1) ? 1.f : 0.f};
@@ -173,30 +202,21 @@
 #pragma unroll
   for (int r = 0; r < RF1; ++r) {
     const int j = gl + NLG * r;
-    const bool ok = act0 && j < NFL;
-    fna1[r] = 0.f; fab1[r] = 0.f; fml1[r] = 0.f;
-    const int ff = j < NB ? 1 + j : 0;   // kw feature index: SiLU 0, logistic j at 1 + j
-    if (ok && j < NB) {
-      fna1[r] = a.plan[a.P1.lg + 2 * (o0 * NB + j)];
-      fab1[r] = a.plan[a.P1.lg + 2 * (o0 * NB + j) + 1];
-    } else if (ok) {
-      fna1[r] = -l2;
-      fml1[r] = 1.f;   // SiLU: h * sigmoid(h)
-    }
-    fwt1[r] = ok ? f2{a.plan[a.P1.kw + (int64_t)0 * (H * NFL) + o0 * NFL + ff],
-                      a.plan[a.P1.kw + (int64_t)1 * (H * NFL) + o0 * NFL + ff]}
-                 : f2{0.f, 0.f};
+    const bool silu = act0 && j == NB;   // SiLU: h * sigmoid(h)
+    const int s = IMG::S_F1 + 4 * r;
+    fna1[r] = silu ? -l2 : LI(s);
+    fab1[r] = LI(s + 1);
+    fml1[r] = silu ? 1.f : 0.f;
+    fwt1[r] = f2{LI(s + 2), LI(s + 3)};
   }
   // ---- layer-0 feature stream: input d = row, job c1 ----
   float xna, xab, xmul, xadd;
   float* xdst;
   {
     const int j = c1;
-    xna = 0.f; xab = 0.f; xmul = 1.f; xadd = 0.f;
+    xna = LI(IMG::S_X); xab = LI(IMG::S_X + 1); xmul = 1.f; xadd = 0.f;
     xdst = &L0.sink;
     if (j < NB) {
-      xna = a.plan[a.P0.lg + 2 * (row * NB + j)];
-      xab = a.plan[a.P0.lg + 2 * (row * NB + j) + 1];
       xdst = &L0.F[row * NFP + 1 + j];
     } else if (j == J_SILU) {
       xna = -l2;
@@ -211,34 +231,35 @@
       xdst = &L0.G[row].z;
     }
   }
-  const bool x_silu = c1 == J_SILU, x_gate = FERRO && c1 == J_GATE, x_exp = FERRO && c1 == J_EXP;
-  const bool x_x = c1 == J_X;
   // knot interval: lane c1 holds knot c1 (and 1/(knot c1+1 - knot c1)); the lane whose knot
   // opens the interval writes u (no LDS round trip on the critical path)
-  const float xknot = c1 < NG ? a.plan[a.P0.knots + row * NG + c1] : __builtin_inff();
+  const float xknot = LI(IMG::S_X + 2);
 
   // knots of hidden input o0: lane cc0 holds knots KT cc0 .. KT cc0 + KT-1
   float hknot[KT];
 #pragma unroll
-  for (int t = 0; t < KT; ++t) {
-    const int kk = KT * cc0 + t;
-    hknot[t] = (act0 && kk < NG) ? a.plan[a.P1.knots + o0 * NG + kk] : __builtin_inff();
-  }
-  // hysteresis state: prev_x of input `row` on the layer-0 gate lane, of input o0 on every lane
-  // of its group (each forms the gate itself) (ferro_class.py:409); per-layer contiguous blocks
-  // (include/fetode.h)
-  float prev0 = 0.f, prev1 = 0.f;
-  if (FERRO && valid) {
-    if (x_gate) prev0 = a.state[b * D + row];
-    if (act0) prev1 = a.state[a.B * D + b * H + o0];
-  }
+  for (int t = 0; t < KT; ++t) hknot[t] = LI(IMG::S_HK + t);
   bool re0 = FERRO && (a.init_mask & 1u), re1 = FERRO && (a.init_mask & 2u);
 
-  float y = valid ? a.y0[b * D + row] : 0.f;   // state dim `row`, replicated over the row
   if (!a.single_eval && valid && own && c1 == 0) a.solution[b * D + row] = y;
+  {
+    v4f* t4 = reinterpret_cast<v4f*>(&s_tab);
+#pragma unroll
+    for (int j = 0; j < NTR; ++j)
+      if ((j + 1) * 64 <= NT4 || tid + 64 * j < NT4) t4[tid + 64 * j] = tv[j];
+  }
+  if (sched0) {   // load_steps(0), load_outs(1)
+    s_dt[tid] = sc_dt;
+    s_hh[tid] = sc_hh;
+    s_h6[tid] = sc_h6;
+    s_ostep[tid] = sc_out && sc_in ? sc_os : -1;
+    s_omode[tid] = sc_out && sc_in ? sc_om : 1;
+    s_oslope[tid] = sc_out && sc_in ? sc_osl : 0.f;
+  }
   __syncthreads();  // tables staged
 
   STAMP_DECL
+  STAMP_PROLOGUE();
   const float c0o = s_c0[o0c], c1o = s_c1[row];  // per-output constants, held in registers
   const float* sp0_o = &s_sp0[o0c * D * SPR * 4];
   // layer 1: the cubic table of edge (o0 -> d = cc0) and the (knot, 1/width) rows of input o0
@@ -369,11 +390,7 @@
     FETODE_MARK("END");
     return kr;
   };
-  // the step / output schedule is staged through LDS in chunks: per-step global loads in the
-  // loop would wait (vmcnt) behind the solution stores of the previous step
-  constexpr int SCH = 32;
-  __shared__ float s_dt[SCH], s_hh[SCH], s_h6[SCH], s_oslope[SCH];
-  __shared__ int s_ostep[SCH], s_omode[SCH];
+  // later schedule chunks (grids past SCH steps / outputs): the first came with the prologue
   auto load_steps = [&](int s0) {
     __syncthreads();
     for (int i = tid; i < SCH && s0 + i < a.n_steps; i += 64) {
@@ -406,8 +423,6 @@
     // rk4 (torchdiffeq rk_common.rk4_alt_step_func op order); the step's first two output
     // slots are read before its stages and consumed after them, with predicated stores
     int sb = 0, jb = 1, jj = 1;
-    load_steps(0);
-    load_outs(1);
     auto run = [&](auto fact_tag) __attribute__((always_inline)) {
       const float third = 1.0f / 3.0f;
       for (int s = 0; s < a.n_steps; ++s) {
@@ -810,8 +825,6 @@
                      : a.method == FETODE_MIDPOINT ? 2 : 1;
       const float third = 1.0f / 3.0f;
       int sb = 0, jb = 1, jj = 1;
-      load_steps(0);
-      load_outs(1);
       for (int s = 0; s < a.n_steps; ++s) {
         if (s - sb == SCH) {
           sb = s;

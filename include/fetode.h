@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define FETODE_ABI_VERSION 2
+#define FETODE_ABI_VERSION 3
 
 enum {
   FETODE_OK = 0,
@@ -138,9 +138,18 @@ int64_t fetode_integrate_dopri5_multipass_max_batch(const fetode_field_t* field)
 int fetode_integrate_dopri5_backward_set_shape(int tpw);
 int fetode_abi_version(void);
 
-/* Size in bytes of the packed "plan" (pre-transformed parameters). */
+/* Size in bytes of the per-layer sections of the packed "plan" (pre-transformed parameters,
+ * SURVEY §8a A3). */
 int64_t fetode_plan_bytes(const fetode_field_t* field);
-/* Build the plan from the parameters; enqueue on stream.  plan: (dev) fetode_plan_bytes bytes. */
+/* Size in bytes of the image block that follows the per-layer sections in the plan buffer: for field
+ * shapes with a specialised fused kernel (the LV [2, 10, 2] KAN / KAN-FET fields) the same values
+ * again, in the order that kernel's lanes consume them (the layout and the lane map:
+ * csrc/fetode_fused4_image.h); 0 for every other shape.  The fused kernels of those shapes read the
+ * block, at byte offset fetode_plan_bytes of the plan.  (ABI 3.) */
+int64_t fetode_plan_image_bytes(const fetode_field_t* field);
+/* Build the plan from the parameters; enqueue on stream (the per-layer sections, then the image
+ * block gathered from them: two launches, capturable).
+ * plan: (dev) fetode_plan_bytes + fetode_plan_image_bytes bytes, 16-byte aligned. */
 int fetode_plan_build(const fetode_field_t* field, void* plan, void* stream);
 
 /* Row length of the compact hysteresis state of `field` (sum of Ferro in_l). */

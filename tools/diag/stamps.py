@@ -15,7 +15,7 @@ PH = {"v8": ["L0 feats+gate+pair", "L0 fw+splines", "unit sum -> h", "L1", "wave
              "stage combine", "outputs+loop"],
       "v6": ["L0 feats+swap", "L0 pair+spline", "row sum -> h", "L1 feats+pair", "L1 spline+sums", "barrier+LDS",
              "stage combine", "outputs+loop"]}.get(
-    KERNEL, ["X feats+bar", "step outputs", "edges0+h", "H feats", "barrier2", "edges1+k", "stage combine", "loop+sched"])
+    KERNEL, ["X feats+bar", "step outputs", "edges0+h", "H feats", "prologue", "edges1+k", "stage combine", "loop+sched"])
 dev = torch.device("cuda:0")
 lib = _lib.load()
 lib.fetode_debug_stamp_buffer.argtypes = [ctypes.c_void_p]
@@ -54,3 +54,7 @@ for B in [int(v) for v in os.environ.get("STAMP_B", "4096,65536").split(",")]:
           f"total {tot.mean():.0f} (p10 {np.percentile(tot, 10):.0f}, p90 {np.percentile(tot, 90):.0f})")
     for p in range(8):
         print(f"   {PH[p]:14s} {st[:, p].mean():8.0f}  ({100 * st[:, p].mean() / tot.mean():4.1f}%)")
+    if PH[4] == "prologue":   # kernel entry to "tables staged", once per launch (fused4 body)
+        pro = st[:, 4] * 136.0
+        print(f"   prologue per launch: {pro.mean():.0f} cycles (p10 {np.percentile(pro, 10):.0f}, p90 "
+              f"{np.percentile(pro, 90):.0f}), {100 * pro.mean() / (tot.mean() * 136.0):.1f} % of the wave's stamped cycles")
