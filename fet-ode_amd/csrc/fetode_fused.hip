@@ -17,6 +17,7 @@
 #include "fetode_dopri_ctl.h"
 #include "fetode_fieldn_plan.h"
 #include "fetode_fused4_image.h"
+#include "fetode_knot_count.h"
 #if (defined(FETODE_EXP_NO_GRIDSUM) || defined(FETODE_EXP_NO_EVAL)) && !defined(FETODE_DIAG)
 #error "FETODE_EXP_NO_GRIDSUM / FETODE_EXP_NO_EVAL are diagnostic knobs: build them with make diag"
 #endif
@@ -64,7 +65,9 @@ __device__ __forceinline__ unsigned long long stamp_now() {
 // waves share each SIMD and run the same instruction stream; the SIMD arbitrates their VALU issue by
 // priority, then age.  The wave in a serial phase (the DPP / permlane reductions, the stage combine,
 // the feature exchange) raises its priority so it gets through the dependent chain, and drops it for
-// the Ferro pair rounds, whose independent instructions then fill the other wave's latency.
+// layer 0's Ferro pair rounds, whose independent instructions then fill the other wave's latency
+// (layer 1's rounds stay at high priority: a drop that takes effect ahead of them costs 4 us per
+// B = 4096 solve, profiles/r08_trim_fwd_ab.log).
 // Measured B = 4096: 159.9 -> 152.6 us per solve (tools/diag/fwd_ab.py, profiles/r06_prio_ab.log);
 // at one wave per SIMD (TPW = 1, v8) there is no partner to yield to and it costs 2 %: TPW = 2 only.
 #define PRIO_HI() \
@@ -208,22 +211,18 @@ struct FusedArgs {
   int64_t img;          // the lane-ordered image block of the plan (fetode_fused4_image.h), in floats
 };
 
-// integer version (knot counts)
-__device__ __forceinline__ int group3_sum_i(int v, int c) {
-  const int s0 = v + __builtin_amdgcn_update_dpp(0, v, 0x101, 0xF, 0xF, false) +
-                 __builtin_amdgcn_update_dpp(0, v, 0x102, 0xF, 0xF, false);
-  const int b1 = __builtin_amdgcn_mov_dpp(s0, 0x111, 0xF, 0xF, false);
-  const int b2 = __builtin_amdgcn_mov_dpp(s0, 0x112, 0xF, 0xF, false);
-  return c == 0 ? s0 : (c == 1 ? b1 : b2);
-}
-// knots <= x among this lane's N knots: one compare + one carry-in add per knot
-template <int N>
-__device__ __forceinline__ int knot_count(float x, const float* kn) {
-  int cnt = 0;
-#pragma unroll
-  for (int t = 0; t < N; ++t)
-    asm volatile("v_cmp_ge_f32 vcc, %1, %2\n\tv_addc_co_u32 %0, vcc, 0, %0, vcc" : "+v"(cnt) : "v"(x), "v"(kn[t]) : "vcc");
-  return cnt;
+// integer group sum (knot counts), formed only where the fused kernels consume it: on the group's
+// lanes 0 and 1, the owners of the hidden unit's two spline edges.  t = v + v[+1]; lane 0 adds v[+2],
+// lane 1 adds v[-1] (integer adds: exact in any order), plus `add`.  Lane 2 gets some other sum of
+// counts: the caller's `add` moves it past the grid, where the clamp sends it to the zero row.
+// Bound-control reads: an out-of-row source reads 0 with no zero-initialised old value to set up
+// (no lane that consumes the sum has one).
+__device__ __forceinline__ int group3_sum_i01(int v, int c, int add) {
+  int t = v + __builtin_amdgcn_update_dpp(0, v, 0x101, 0xF, 0xF, true);         // row_shl:1
+  asm("" : "+v"(t));   // one v_add_u32_dpp (else the read becomes a move of its own under a v_add3)
+  const int a = __builtin_amdgcn_update_dpp(0, v, 0x102, 0xF, 0xF, true);       // row_shl:2
+  const int b = __builtin_amdgcn_update_dpp(0, v, 0x111, 0xF, 0xF, true);       // row_shr:1
+  return t + (c == 0 ? a : b) + add;
 }
 
 // sum over lanes 3k, 3k+1, 3k+2 of a row (k < 5), result on all three

@@ -73,6 +73,7 @@
   constexpr int SCH = 64;
   __shared__ float s_dt[SCH], s_hh[SCH], s_h6[SCH], s_oslope[SCH];
   __shared__ int s_ostep[SCH], s_omode[SCH];
+  __shared__ f2 s_zkr[NI + 1];   // (0, 0) rows: u = 0 on the lanes whose layer-1 spline value is not used
 
   const int tid = threadIdx.x;
   const int hh = tid >> 5;                                   // half-wave
@@ -137,6 +138,7 @@
     return li[s / 4][s % 4];
   };
   for (int i = lane; i < FLEN0; i += 32) L0.F[i] = 0.f;  // pads stay zero (finite x zero weight)
+  if (tid <= NI) s_zkr[tid] = f2{0.f, 0.f};
 
   const bool fact = FERRO && a.plan[a.img] <= a.factor_limit && a.plan[a.img + 1] <= a.factor_limit;   // the guard words
   const float l2 = FETODE_LOG2E;
@@ -264,7 +266,8 @@
   const float* sp0_o = &s_sp0[o0c * D * SPR * 4];
   // layer 1: the cubic table of edge (o0 -> d = cc0) and the (knot, 1/width) rows of input o0
   const float* sp1_e = &s_sp1[((gl < D ? gl : 0) * H + o0c) * SPR * 4];
-  const f2* kr1_o = &s_kr1[o0c * SPR];
+  // (lanes that own no layer-1 spline edge read zero rows: see the hidden knot interval below)
+  const f2* kr1_o = (act0 && gl < D) ? &s_kr1[o0c * SPR] : s_zkr;
   const int fofs0 = gl * FPL0;
   const bool spl0 = act0 && gl < D;  // lanes owning a layer-0 spline edge (input si)
   const int si0 = spl0 ? gl : 0;
@@ -324,9 +327,15 @@
     // (3) layer 1 on the group of hidden input o0 (v7): partial sums of BOTH outputs in acc01
     f2 acc01 = splat(0.0f);
     {
-      // knot interval of h: KT compares per lane, summed over the group
+      // knot interval of h: each lane counts its KT knots, the counts meet on the group's lanes 0
+      // and 1, the owners of the unit's spline edges (dsel1)
       // (a non-finite h counts 0 or all 12 knots: the zero row, no finiteness test needed)
-      const int mm = group3_sum_i(knot_count<KT>(h, hknot), cc0) - 1;
+      // Every other lane holds some other sum of counts: the clamp keeps its index inside the
+      // tables, and its (knot, 1/width) rows are the zero rows of s_zkr, so its u is 0 and its spline
+      // value a finite c0 whenever h is finite (a wrong interval's own u could overflow the cubic),
+      // which meets dsel1 = (0, 0); for a non-finite h lanes 0 and 1 already give the reference's
+      // NaN to both outputs.
+      const int mm = group3_sum_i01(knot_count<KT>(h, hknot), cc0, -1);
       const int mfix = (unsigned)mm < (unsigned)NI ? mm : NI;
       // spline operands by interval (the zero row NI holds (0, 0): u = 0 for finite h, NaN
       // otherwise, as the reference's bases); their LDS latency hides under the pairs
@@ -343,7 +352,8 @@
         prev1 = h;   // ferro_class.py:409
         re1 = false;
         const f2 ew = f2{e, w}, xp = f2{h, 0.0f};
-        PRIO_LO();
+        // (no priority drop for these pair rounds: where one takes effect ahead of them the B = 4096
+        // solve is 4 us slower, profiles/r08_trim_fwd_ab.log; the phase stays at high priority)
         if constexpr (NSL1 > 0) sgl = v4_single<F_>(ew, xp, es1, k2s1, kEs1, cps1, 0.0f, a.P1.gsl2e);
 #pragma unroll
         for (int r = 0; r < NPL1; ++r) acc01 = v4_pair<F_>(ew, xp, ep1[r], k21[r], kE1[r], cp1[r], acc01, a.P1.gsl2e);
