@@ -272,6 +272,14 @@ __device__ __forceinline__ void v4_g(const V4Lds<IN, FLEN>& L, int i, f2& ew, f2
   xp = g2[1];
   asm volatile("" : "+v"(ew), "+v"(xp));
 }
+// An LDS read that is issued where it is written (the batched operand reads of v4_edges): volatile, so
+// the compiler neither narrows it nor moves it across another memory operation, and through a pointer
+// typed as LDS (a volatile access keeps the generic pointer's flat instruction otherwise).
+typedef float f4r __attribute__((ext_vector_type(4)));
+template <typename T>
+__device__ __forceinline__ T lds_now(const T* p) {
+  return *(const volatile __attribute__((address_space(3))) T*)p;
+}
 
 // one Ferro element pair of one input: acc += cps * tanh(k (x - Ec m)) for both
 template <bool FACT>
@@ -314,18 +322,58 @@ __device__ __forceinline__ float v4_single(f2 ew, f2 xp, float ep, float k2, flo
 // spline table reads issue straight after the exchange instead of behind an LDS read of the interval.
 // A non-finite x counts 0 or all knots (lanes >= NG hold +inf): the zero row, whose (x - 0) * 0 is the
 // reference's NaN — no separate finiteness test.
-template <int IN, int FLEN, int NI, int NPL, int NSL, int FPL, bool FERRO, bool FACT>
+// (round 9) EB: the phase's LDS operands are read in one batch straight after the exchange — the
+// {e, w, x, pad} rows of every round, x_si, the two table rows and (EBF) the feature chunks — and each
+// round takes its row's halves as its packed operands where it starts: the waits count down
+// (lgkmcnt(n)) and only the first is exposed.  None of the reads depends on anything the phase
+// computes.  EB = false is the former form, a read per round behind the previous round's pin; the
+// arithmetic and its order are the same in both.
+template <int IN, int FLEN, int NI, int NPL, int NSL, int FPL, bool FERRO, bool FACT, bool EB = false,
+          bool EBF = false, unsigned SAME = 0u>
 __device__ __forceinline__ float v4_edges(const V4Lds<IN, FLEN>& L, const float* sp_o, const f2* kr,
                                           const int* gi, const f2* ep, const f2* k2, const f2* kE, const f2* cp,
                                           const f2* fw, int fofs, bool spl, int si, float gsl2e, int gis, float eps,
                                           float k2s, float kEs, float cps, uint64_t bal, int bbase) {
+  static_assert(!EB || FERRO, "the batched form is the Ferro rounds'");
+  static_assert(!EBF || (EB && FPL % 4 == 0), "feature chunks join the batch as float4s");
+  f4r rs = {0.f, 0.f, 0.f, 0.f}, rp[NPL > 0 ? NPL : 1], fv[FPL / 4 > 0 ? FPL / 4 : 1];
+  if constexpr (EB) {
+    if constexpr (NSL > 0) rs = lds_now(reinterpret_cast<const f4r*>(&L.G[gis]));
+#pragma unroll
+    for (int r = 0; r < NPL; ++r) {
+      if (r > 0 && ((SAME >> r) & 1u))
+        rp[r] = rp[r - 1];
+      else
+        rp[r] = lds_now(reinterpret_cast<const f4r*>(&L.G[gi[r]]));
+    }
+    __builtin_amdgcn_sched_barrier(0);   // the rows ahead of the table reads' address arithmetic
+  }
   // spline operands first (table reads by interval), so their latency hides under the pairs
   const int mraw = (int)__builtin_popcountll((bal >> (bbase + 16 * si)) & 0xFFFFull) - 1;
   const int msi = (unsigned)mraw < (unsigned)NI ? mraw : NI;
-  const float xsi = L.G[si].z;
   // the cubic tables' rows are NI + 2 float4 apart (NI + 1 entries and a pad, fused4_kernel)
-  const float4 cf = *reinterpret_cast<const float4*>(&sp_o[(si * (NI + 2) + msi) * 4]);
-  const f2 kw = kr[si * (NI + 1) + msi];
+  const auto ld = [](auto* p) __attribute__((always_inline)) {
+    if constexpr (EB) return lds_now(p);
+    else return *p;
+  };
+  const auto ld4 = [](const float* p) __attribute__((always_inline)) {
+    if constexpr (EB) {
+      const f4r t = lds_now(reinterpret_cast<const f4r*>(p));
+      return make_float4(t.x, t.y, t.z, t.w);
+    } else {
+      return *reinterpret_cast<const float4*>(p);
+    }
+  };
+  const float xsi = ld(&L.G[si].z);
+  const float4 cf = ld4(&sp_o[(si * (NI + 2) + msi) * 4]);
+  const f2 kw = ld(&kr[si * (NI + 1) + msi]);
+  if constexpr (EB) {
+    if constexpr (EBF) {
+#pragma unroll
+      for (int f = 0; f < FPL / 4; ++f) fv[f] = lds_now(reinterpret_cast<const f4r*>(&L.F[fofs]) + f);
+    }
+    __builtin_amdgcn_sched_barrier(0);   // every read issued before the first round starts
+  }
   f2 acc = splat(0.0f);
   float sgl = 0.0f;
   if constexpr (FERRO) {
@@ -333,19 +381,35 @@ __device__ __forceinline__ float v4_edges(const V4Lds<IN, FLEN>& L, const float*
     // latencies interleave with theirs
     if constexpr (NSL > 0) {
       f2 ew, xp;
-      v4_g(L, gis, ew, xp);
+      if constexpr (EB) {
+        ew = rs.xy;
+        xp = rs.zw;
+      } else {
+        v4_g(L, gis, ew, xp);
+      }
       sgl = v4_single<FACT>(ew, xp, eps, k2s, kEs, cps, 0.0f, gsl2e);
     }
 #pragma unroll
     for (int r = 0; r < NPL; ++r) {
       f2 ew, xp;
-      v4_g(L, gi[r], ew, xp);
+      if constexpr (EB) {   // the halves of the loaded quad (sub-registers: no moves, no pin needed)
+        ew = rp[r].xy;
+        xp = rp[r].zw;
+      } else {
+        v4_g(L, gi[r], ew, xp);
+      }
       acc = v4_pair<FACT>(ew, xp, ep[r], k2[r], kE[r], cp[r], acc, gsl2e);
     }
   }
   const float u = (xsi - kw.x) * kw.y;
   // feature weights after the pairs (measured: 191 vs 201 us per B = 4096 solve with them first)
-  if constexpr (FPL % 4 == 0) {  // chunk offsets are 16-byte aligned: ds_read_b128
+  if constexpr (EBF) {
+#pragma unroll
+    for (int f = 0; f < FPL / 4; ++f) {
+      acc = pfma(fw[2 * f], f2{fv[f].x, fv[f].y}, acc);
+      acc = pfma(fw[2 * f + 1], f2{fv[f].z, fv[f].w}, acc);
+    }
+  } else if constexpr (FPL % 4 == 0) {  // chunk offsets are 16-byte aligned: ds_read_b128
     const float4* Fp = reinterpret_cast<const float4*>(&L.F[fofs]);
 #pragma unroll
     for (int f = 0; f < FPL / 4; ++f) {

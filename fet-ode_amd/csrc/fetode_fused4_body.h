@@ -29,6 +29,24 @@
   constexpr int FPL0 = ((D * NFP + NLG - 1) / NLG + 3) & ~3;
   constexpr int RF1 = (NFL + NLG - 1) / NLG;                 // feature rounds of a hidden input (SiLU + NB)
   constexpr int FLEN0 = (NLG * FPL0 > D * NFP ? NLG * FPL0 : D * NFP);
+  // layer 0's edge operands read in one batch (v4_edges, EB): every KAN-FET instantiation (with the
+  // shared rows below none gains scratch or loses an occupancy step); the feature chunks join the
+  // batch (EBF, 8 more registers) in the rk4 kernels only: the generic and taped kernels would drop
+  // from 3 to 2 waves per SIMD, the taped dopri5 and multi-pass kernels would spill
+  constexpr bool EB0 = FERRO, EBF0 = EB0 && HOT;
+  // bit r: round r reads the row round r - 1 read, on every lane (gi0 below): it is read once
+  constexpr unsigned SAME0 = [] {
+    unsigned m = 0;
+    for (int r = 1; r < NPL0; ++r) {
+      bool same = true;
+      for (int l = 0; l < NLG; ++l) {
+        const int p1 = l * NPL0 + r, p0 = p1 - 1;
+        same = same && (p1 < D * KP ? p1 / KP : 0) == (p0 < D * KP ? p0 / KP : 0);
+      }
+      if (same) m |= 1u << r;
+    }
+    return m;
+  }();
   if constexpr (DOPRI) {
     if (a.dp.xr_world > 1 && blockIdx.x == gridDim.x - 1) {   // the cross-rank exchange workgroup
       xrank_comm(a.dp);
@@ -153,7 +171,7 @@
     const bool ok = act0 && P < D * KP;
     int i = ok ? P / KP : 0;
     asm volatile("" : "+v"(i));  // keep in a VGPR (no per-evaluation rematerialisation)
-    gi0[r] = i;
+    gi0[r] = i;                  // (SAME0 above restates this row rule at compile time)
     const int s = IMG::S_P0 + 8 * r;
     ep0[r] = f2{gexp(LI(s)), gexp(LI(s + 1))};
     k20[r] = f2{LI(s + 2), LI(s + 3)};
@@ -312,9 +330,9 @@
     FETODE_MARK("EDGES0");
     PRIO_LO();
     // (2) layer-0 edges -> h_o on the group of 3
-    float h = v4_edges<D, FLEN0, NI, NPL0, NSL0, FPL0, FERRO, F_>(L0, sp0_o, s_kr0, gi0, ep0, k20, kE0, cp0, fw0,
-                                                                  fofs0, spl0, si0, a.P0.gsl2e, gs0, es0, k2s0, kEs0,
-                                                                  cps0, bal0, TPW == 2 ? 32 * g : 0);
+    float h = v4_edges<D, FLEN0, NI, NPL0, NSL0, FPL0, FERRO, F_, EB0, EBF0, SAME0>(
+        L0, sp0_o, s_kr0, gi0, ep0, k20, kE0, cp0, fw0, fofs0, spl0, si0, a.P0.gsl2e, gs0, es0, k2s0, kEs0, cps0, bal0,
+        TPW == 2 ? 32 * g : 0);
     if constexpr (TPW == 1) {   // the two halves' partial edge sums (the same sum on both halves)
       float p = h, q2 = h;
       permlane32_swap(p, q2);
