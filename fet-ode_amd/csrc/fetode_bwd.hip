@@ -678,6 +678,7 @@ constexpr int64_t kSumBlocks = 1024;  // param_sum_kernel blocks per layer (= pa
 // 386 + 109 us vs 496 us with every sum in the sweep — kansum recomputes the features; kept as
 // the alternative).
 int g_bwd_v7 = -1;
+int g_bwd_tpw = 0;  // fetode_backward_set_tpw
 int v7_mode() {
   if (g_bwd_v7 < 0) {
     const char* v = getenv("FETODE_BWD_V7");
@@ -771,15 +772,24 @@ int fetode_backward_set_v7(int32_t mode) {
   return prev;
 }
 
+int fetode_backward_set_tpw(int32_t tpw) {
+  const int prev = g_bwd_tpw;
+  if (tpw >= 0 && tpw <= 2) g_bwd_tpw = tpw;
+  return prev;
+}
+
 int fetode_fused_backward_supported(const fetode_field_t* f) {
   if (validate_field(f) != FETODE_OK) return 0;
   return find_bwd(f) != nullptr || fieldn_shape_supported(f);
 }
 
 // the one-kernel sweep at one trajectory per wave while those waves fit one resident round
-// (latency-bound small batches: half the VJP jobs per lane), else e->tpw
+// (latency-bound small batches: half the VJP jobs per lane), else e->tpw.
+// fetode_backward_set_tpw: 0 automatic, 1 / 2 force that shape where the entry has it
 int fixed_tpw(const BwdEntry* e, int64_t B) {
   if (!e->fn1) return e->tpw;
+  if (g_bwd_tpw == 1) return 1;
+  if (g_bwd_tpw == 2) return e->tpw;
   static int64_t cap = -1;
   if (cap < 0 && getenv("FETODE_BWD_TPW1") && atoi(getenv("FETODE_BWD_TPW1")) == 0) cap = 0;  // A/B knob
   if (cap < 0) {

@@ -469,6 +469,12 @@ int fetode_backward_set_split(int32_t enable);
  * summation order.  Returns the previous setting; mode < 0 only queries.  Call before sizing
  * workspaces. */
 int fetode_backward_set_v7(int32_t mode);
+/* Trajectories per wave of the one-kernel [2, 10, 2] KAN-FET sweep: 0 = automatic (one per wave while
+ * those waves fill at most half of the resident capacity, else two; the default), 1 / 2 = that shape
+ * at every batch where the field's entry has it (the workspace size, the partial rows and the launch
+ * follow it; with fetode_backward_set_v7(1) the lane-group sweep follows it too).  Returns the previous
+ * setting; tpw < 0 (or > 2) only queries.  Call before sizing workspaces. */
+int fetode_backward_set_tpw(int32_t tpw);
 /* Workspace bytes for fetode_integrate_fixed_backward of a (method, n_steps) forward at batch B
  * (the split path records every evaluation's adjoints: n_evals * B * (D + H) floats of it). */
 int64_t fetode_integrate_fixed_backward_workspace(const fetode_field_t* field, int32_t method, int32_t n_steps,

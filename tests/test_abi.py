@@ -91,6 +91,35 @@ def test_v8_workgroup_shape_switch(lib):
         f(prev)
 
 
+def test_backward_tpw_switch():
+    """fetode_backward_set_tpw: 0 / 1 / 2 set, anything else only queries, the previous value comes
+    back; and the sweep's workspace size follows the forced shape (host code only: at B = 7 one
+    trajectory per wave needs 8 partial rows, two per wave 4), the automatic choice being one of the
+    two, while the stateless KAN entry, which has the one shape, ignores the knob."""
+    import fet_ode_amd as F
+    lib = F._lib.load()
+    f = lib.fetode_backward_set_tpw
+    prev, prev_v7 = f(-1), lib.fetode_backward_set_v7(0)
+    try:
+        assert prev in (0, 1, 2) and f(-1) == prev
+        assert f(1) == prev and f(-1) == 1
+        for bad in (-7, 3, 1 << 20):
+            assert f(bad) == 1 and f(-1) == 1
+        assert f(2) == 1 and f(0) == 2 and f(-1) == 0
+        h, hk = _lv_field(F), _lv_field(F, False)
+        ws = lib.fetode_integrate_fixed_backward_workspace
+        size, size_kan = {}, {}
+        for tpw in (0, 1, 2):
+            f(tpw)
+            size[tpw] = ws(h.ref, F._lib.RK4, 1, 7)
+            size_kan[tpw] = ws(hk.ref, F._lib.RK4, 1, 7)
+        assert 0 < size[2] < size[1] and size[0] in (size[1], size[2]), size
+        assert size_kan[0] > 0 and size_kan[0] == size_kan[1] == size_kan[2], size_kan
+    finally:
+        f(prev)
+        lib.fetode_backward_set_v7(prev_v7)
+
+
 @pytest.mark.parametrize("env,expect", [(None, 2), ("1", 1), ("2", 2), ("0", 2), ("4", 2), ("x", 2), ("", 2)])
 def test_v8_workgroup_shape_env(lib, env, expect):
     """FETODE_V8_TPB is read once at load: 1 or 2 is taken, anything else leaves the default of 2."""
