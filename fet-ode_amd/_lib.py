@@ -109,6 +109,8 @@ SIGNATURES = {
     "fetode_fused_set_tpw1_range": (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int64]),
     "fetode_fused_set_v8_range": (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int64]),
     "fetode_fused_set_v8_tpb": (ctypes.c_int, [ctypes.c_int]),
+    "fetode_fused_set_wave_skew": (ctypes.c_int, [ctypes.c_int]),
+    "fetode_fused_set_wave_prio": (ctypes.c_int, [ctypes.c_int]),
     "fetode_fused_get_batch_ranges": (ctypes.c_int, [ctypes.c_void_p]),
     "fetode_dopri5_set_spin_limit": (ctypes.c_uint32, [ctypes.c_uint32]),
     "fetode_dopri5_set_multipass": (ctypes.c_int, [ctypes.c_int]),

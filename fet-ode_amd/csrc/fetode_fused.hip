@@ -61,6 +61,58 @@ __device__ __forceinline__ unsigned long long stamp_now() {
 #define STAMP_FLUSH()
 #endif
 
+// Relative progress of the two waves that share a SIMD (diagnostic build only: make progress,
+// tools/diag/wave_phase.py).  The headline instantiation alone (the body's SKEW) reads the clock
+// eight times per solve: at entry, at "tables staged", after steps 1, 9, 17, 25 and the last, and at
+// exit; read k is kept on lane k of one 64-bit register and the wave's row (the reads, blockIdx.x,
+// HW_ID, XCC_ID) leaves with one vector store after the solve.  Nothing is read per evaluation, so
+// the schedule inside a step is the shipped kernel's.
+#ifdef FETODE_PROGRESS
+__device__ unsigned long long* g_fetode_progress;
+__device__ long long g_fetode_progress_rows;
+constexpr int kProgressRow = 16;   // 64-bit words per wave
+__device__ __forceinline__ unsigned long long progress_now() {
+  unsigned long long t;
+  __builtin_amdgcn_sched_barrier(0);
+  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
+  __builtin_amdgcn_sched_barrier(0);
+  return t;
+}
+#define PROGRESS_DECL              \
+  unsigned long long pg_v = 0;     \
+  int pg_n = 0;
+#define PROGRESS_MARK()                                     \
+  do {                                                      \
+    if constexpr (SKEW) {                                   \
+      const unsigned long long pg_t = progress_now();       \
+      pg_v = (int)threadIdx.x == pg_n ? pg_t : pg_v;        \
+      ++pg_n;                                               \
+    }                                                       \
+  } while (0)
+#define PROGRESS_STEP(s)                                                                                \
+  do {                                                                                                  \
+    if constexpr (SKEW)                                                                                 \
+      if (((((s) & 7) == 0 && (s) + 8 < a.n_steps) || (s) + 1 == a.n_steps) && pg_n < 7) PROGRESS_MARK(); \
+  } while (0)
+#define PROGRESS_FLUSH()                                                                               \
+  do {                                                                                                 \
+    if constexpr (SKEW) {                                                                              \
+      pg_n = 7;                                                                                        \
+      PROGRESS_MARK();                                                                                 \
+      const unsigned pg_hw = __builtin_amdgcn_s_getreg(4 | (31 << 11));    /* HW_ID, 32 bits */        \
+      const unsigned pg_xcc = __builtin_amdgcn_s_getreg(20 | (3 << 11));   /* XCC_ID, 4 bits */        \
+      pg_v = threadIdx.x == 8 ? blockIdx.x : threadIdx.x == 9 ? pg_hw : threadIdx.x == 10 ? pg_xcc : pg_v; \
+      if (threadIdx.x < 11 && g_fetode_progress && (long long)blockIdx.x < g_fetode_progress_rows)     \
+        g_fetode_progress[(long long)blockIdx.x * kProgressRow + threadIdx.x] = pg_v;                  \
+    }                                                                                                  \
+  } while (0)
+#else
+#define PROGRESS_DECL
+#define PROGRESS_MARK()
+#define PROGRESS_STEP(s)
+#define PROGRESS_FLUSH()
+#endif
+
 // Wave priority around an evaluation's serial phases (round 6).  At two trajectories per wave two
 // waves share each SIMD and run the same instruction stream; the SIMD arbitrates their VALU issue by
 // priority, then age.  The wave in a serial phase (the DPP / permlane reductions, the stage combine,
@@ -70,13 +122,24 @@ __device__ __forceinline__ unsigned long long stamp_now() {
 // B = 4096 solve, profiles/r08_trim_fwd_ab.log).
 // Measured B = 4096: 159.9 -> 152.6 us per solve (tools/diag/fwd_ab.py, profiles/r06_prio_ab.log);
 // at one wave per SIMD (TPW = 1, v8) there is no partner to yield to and it costs 2 %: TPW = 2 only.
+// Round 10: at equal priority the SIMD serves the older wave, and the waves of a pair stand at equal
+// priority most of the time, so the younger wave (dispatched in the grid's second round) ran at half
+// the older one's speed and then a third of the solve alone (profiles/r10_phase_before.txt).  The
+// headline kernel can run the younger wave's first steps with its own pair of levels (PL = 1, a second
+// instantiation of the step loop: s_setprio takes an immediate; fetode_fused_set_wave_prio).
+#ifndef FETODE_YPRIO_HI
+#define FETODE_YPRIO_HI 2
+#endif
+#ifndef FETODE_YPRIO_LO
+#define FETODE_YPRIO_LO 1
+#endif
 #define PRIO_HI() \
   do {            \
-    if constexpr (TPW == 2) __builtin_amdgcn_s_setprio(1); \
+    if constexpr (TPW == 2) __builtin_amdgcn_s_setprio(PL ? FETODE_YPRIO_HI : 1); \
   } while (0)
 #define PRIO_LO() \
   do {            \
-    if constexpr (TPW == 2) __builtin_amdgcn_s_setprio(0); \
+    if constexpr (TPW == 2) __builtin_amdgcn_s_setprio(PL ? FETODE_YPRIO_LO : 0); \
   } while (0)
 
 #ifdef FETODE_ISA_MARKERS
@@ -205,8 +268,15 @@ struct FusedArgs {
   uint32_t init_mask;
   float* tape;            // (n_evals, B, D+H) layer inputs of every evaluation (training), or null
   int32_t single_eval;  // 1: eval_out = field(y0) once (fetode_field_forward)
+  int32_t pair_from;    // the first workgroup of the grid's second round: the device's SIMD count (see pair)
   float* eval_out;
   float factor_limit;   // kFactorLimit (FETODE_FACTOR_LIMIT=-1 disables the factored gate: diagnostics)
+  // the headline rk4 kernel's treatment of the younger wave of a SIMD pair (launch_fused, fused4 body):
+  // bits 0..6 the wave skew in s_sleep units, bits 8..14 the priority lift's per cent of the steps; 0:
+  // none, or no partner exists.
+  // (This and pair_from stand in padding: no other member's kernarg offset moves, every other kernel's
+  // code stays as it was.)
+  int32_t pair;
   DopriParams dp;       // dp.on: the whole dopri5 solve in this launch (fetode_integrate_dopri5)
   int64_t img;          // the lane-ordered image block of the plan (fetode_fused4_image.h), in floats
 };
@@ -1409,6 +1479,31 @@ int g_v8_tpb = [] {   // trajectories per v8 workgroup (1: two waves, 2: four wa
   const int v = e ? atoi(e) : 2;
   return v == 1 || v == 2 ? v : 2;   // anything else is ignored: the default stays
 }();
+// Wave skew of the headline rk4 kernel (fused4 body): s_sleep units (64 cycles
+// each) one wave of every SIMD pair sleeps before its first step; 0: off.  env FETODE_WAVE_SKEW, where
+// anything but a whole number is ignored and a number is clamped to s_sleep's range.
+constexpr int kWaveSkewMax = 127, kWaveSkewDefault = 0;
+int clamp_skew(long v) { return v < 0 ? 0 : v > kWaveSkewMax ? kWaveSkewMax : (int)v; }
+int g_wave_skew = [] {
+  const char* e = getenv("FETODE_WAVE_SKEW");
+  if (!e || !*e) return kWaveSkewDefault;
+  char* end = nullptr;
+  const long v = strtol(e, &end, 10);
+  return *end ? kWaveSkewDefault : clamp_skew(v);
+}();
+// Priority lift of the same kernel: the younger wave of every SIMD pair runs this per cent of its steps,
+// the first ones, with the lifted PRIO_HI / PRIO_LO levels; 0: off.  env FETODE_WAVE_PRIO (a whole
+// number 0..100, anything else is ignored).  Measured B = 4096 (profiles/r10_phase_variants.log, us per
+// solve): off 135.3, 50 % 128.4, 62 % 126.8, 67 % 126.1, 72 % 127.1, 100 % 134.4 (the lagging wave
+// swapped); the lead is 2 : 1 either way, so the two end together where 2/3 of the steps are lifted.
+constexpr int kWavePrioDefault = 67;
+int g_wave_prio = [] {
+  const char* e = getenv("FETODE_WAVE_PRIO");
+  if (!e || !*e) return kWavePrioDefault;
+  char* end = nullptr;
+  const long v = strtol(e, &end, 10);
+  return *end || v < 0 || v > 100 ? kWavePrioDefault : (int)v;
+}();
 uint32_t g_dp_spin_limit = 0;   // fetode_dopri5_set_spin_limit (0: the built-in limits)
 
 const FusedEntry* find_fused(const fetode_field_t* f) {
@@ -1849,6 +1944,22 @@ int launch_fused(const fetode_field_t* f, FusedArgs& a, void* stream) {
     hipLaunchKernelGGL(fn, dim3((unsigned)a.B), dim3(192), 0, (hipStream_t)stream, a);
   } else {                              // v4: two trajectories per one-wave workgroup
     const fused_fn fn = a.tape ? (rk4 ? e->fn_rk4_tape : e->fn_tape) : (rk4 ? e->fn_rk4 : e->fn);
+    // the wave skew and the priority lift: only where the grid holds more waves than the device has
+    // SIMDs (a partner exists) and at most two per SIMD (every wave is resident from the start and
+    // workgroups b and b + SIMD count share a SIMD: the arrangement that was measured)
+    a.pair = a.pair_from = 0;
+    if ((g_wave_skew > 0 || g_wave_prio) && rk4 && !a.tape && f->ferro) {
+      static const int n_simd = [] {
+        int dev = 0, n_cu = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+          return 0;
+        return 4 * n_cu;
+      }();
+      if (n_simd > 0 && nblk(a.B, 2) > n_simd && nblk(a.B, 2) <= 2 * n_simd) {
+        a.pair = g_wave_skew | g_wave_prio << 8;
+        a.pair_from = n_simd;
+      }
+    }
     hipLaunchKernelGGL(fn, dim3(nblk(a.B, 2)), dim3(64), 0, (hipStream_t)stream, a);
   }
   LAUNCH_CHECK();
@@ -1886,6 +1997,14 @@ int fetode_debug_stamp_buffer(void* p) {
 }
 #endif
 
+#ifdef FETODE_PROGRESS
+// rows x 16 64-bit words, one row per workgroup of the headline kernel (null: off)
+int fetode_debug_progress_buffer(void* p, long long rows) {
+  if (hipMemcpyToSymbol(HIP_SYMBOL(g_fetode_progress_rows), &rows, sizeof(rows)) != hipSuccess) return FETODE_EHIP;
+  return hipMemcpyToSymbol(HIP_SYMBOL(g_fetode_progress), &p, sizeof(p)) == hipSuccess ? FETODE_OK : FETODE_EHIP;
+}
+#endif
+
 uint32_t fetode_dopri5_set_spin_limit(uint32_t polls) {
   const uint32_t prev = g_dp_spin_limit;
   g_dp_spin_limit = polls;
@@ -1915,6 +2034,18 @@ int64_t fetode_fused_set_v8_range(int64_t lo, int64_t hi) {
 int fetode_fused_set_v8_tpb(int tpb) {
   const int prev = g_v8_tpb;
   if (tpb == 1 || tpb == 2) g_v8_tpb = tpb;
+  return prev;
+}
+
+int fetode_fused_set_wave_skew(int units) {
+  const int prev = g_wave_skew;
+  if (units >= 0) g_wave_skew = clamp_skew(units);
+  return prev;
+}
+
+int fetode_fused_set_wave_prio(int percent) {
+  const int prev = g_wave_prio;
+  if (percent >= 0 && percent <= 100) g_wave_prio = percent;
   return prev;
 }
 

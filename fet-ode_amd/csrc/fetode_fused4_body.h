@@ -54,6 +54,12 @@
     }
   }
   STAMP_ENTRY
+  // the headline instantiation (KAN-FET rk4 inference, two trajectories per wave): the only one whose
+  // waves share a SIMD for a whole solve with nothing to synchronise them, and the only one with the
+  // wave skew below (and the progress build's clock reads); every other one compiles without either
+  constexpr bool SKEW = !MP && FERRO && HOT && !DOPRI && !TAPE && TPW == 2;
+  PROGRESS_DECL
+  PROGRESS_MARK();
   constexpr int KT = (NG + 2) / 3;                   // knots per group lane
   static_assert(3 * KT >= NG, "knots per group lane");
   // The parameters arrive in the plan's image block (fetode_fused4_image.h: the one definition of
@@ -277,6 +283,25 @@
     s_oslope[tid] = sc_out && sc_in ? sc_osl : 0.f;
   }
   __syncthreads();  // tables staged
+  PROGRESS_MARK();
+  // The younger wave of a SIMD pair: the grid's second round of workgroups (a.pair_from: the device's
+  // SIMD count; partners are blockIdx.x and blockIdx.x + that count, profiles/r10_phase_before.txt).
+  // a.pair is 0 where the grid leaves the waves no partner (launch_fused).  Wave-uniform: scalar code.
+  const bool younger = SKEW && a.pair != 0 && (int)blockIdx.x >= a.pair_from;
+  if constexpr (SKEW) {
+    // Wave skew (fetode_fused_set_wave_skew): the younger wave sleeps once
+    // here, so the pair runs the solve that much further apart.
+    if (younger && (a.pair & 127)) {   // s_sleep takes an immediate: the count in binary
+      const int sk = a.pair;
+      if (sk & 64) __builtin_amdgcn_s_sleep(64);
+      if (sk & 32) __builtin_amdgcn_s_sleep(32);
+      if (sk & 16) __builtin_amdgcn_s_sleep(16);
+      if (sk & 8) __builtin_amdgcn_s_sleep(8);
+      if (sk & 4) __builtin_amdgcn_s_sleep(4);
+      if (sk & 2) __builtin_amdgcn_s_sleep(2);
+      if (sk & 1) __builtin_amdgcn_s_sleep(1);
+    }
+  }
 
   STAMP_DECL
   STAMP_PROLOGUE();
@@ -301,8 +326,10 @@
   float* tape_b = taping ? a.tape + (valid ? b : 0) * TW : nullptr;
   const int64_t tape_stride = a.B * TW;
   uint64_t bal0 = 0;   // the feature phase's knot ballot (both trajectories' rows of both inputs)
-  auto eval_body = [&](float xin, auto fact_tag) __attribute__((always_inline)) -> float {
+  // (prio_tag: 1 in the younger wave's step loop of the headline kernel, the PRIO_HI / PRIO_LO levels)
+  auto eval_body = [&](float xin, auto fact_tag, auto prio_tag) __attribute__((always_inline)) -> float {
     constexpr bool F_ = decltype(fact_tag)::value;
+    constexpr int PL = decltype(prio_tag)::value;
     STAMP(6);
     FETODE_MARK("X_FEAT");
     {
@@ -372,9 +399,16 @@
         const f2 ew = f2{e, w}, xp = f2{h, 0.0f};
         // (no priority drop for these pair rounds: where one takes effect ahead of them the B = 4096
         // solve is 4 us slower, profiles/r08_trim_fwd_ab.log; the phase stays at high priority)
+        // (re-tested with the round-10 priority lift, -DFETODE_EXP_L1_DROP: profiles/r10_phase_variants.log)
+#ifdef FETODE_EXP_L1_DROP
+        PRIO_LO();
+#endif
         if constexpr (NSL1 > 0) sgl = v4_single<F_>(ew, xp, es1, k2s1, kEs1, cps1, 0.0f, a.P1.gsl2e);
 #pragma unroll
         for (int r = 0; r < NPL1; ++r) acc01 = v4_pair<F_>(ew, xp, ep1[r], k21[r], kE1[r], cp1[r], acc01, a.P1.gsl2e);
+#ifdef FETODE_EXP_L1_DROP
+        PRIO_HI();
+#endif
       }
       // the group's features (SiLU + NB logistic), each weighted for both outputs
 #pragma unroll
@@ -446,14 +480,16 @@
   };
   using FT = std::integral_constant<bool, true>;
   using FF = std::integral_constant<bool, false>;
+  using P0 = std::integral_constant<int, 0>;
+  using P1 = std::integral_constant<int, 1>;
 
   if constexpr (HOT) {
     // rk4 (torchdiffeq rk_common.rk4_alt_step_func op order); the step's first two output
     // slots are read before its stages and consumed after them, with predicated stores
     int sb = 0, jb = 1, jj = 1;
-    auto run = [&](auto fact_tag) __attribute__((always_inline)) {
+    auto run = [&](auto fact_tag, auto prio_tag, int s_from, int s_to) __attribute__((always_inline)) {
       const float third = 1.0f / 3.0f;
-      for (int s = 0; s < a.n_steps; ++s) {
+      for (int s = s_from; s < s_to; ++s) {
         if (s - sb == SCH) {
           sb = s;
           load_steps(s);
@@ -467,10 +503,10 @@
         const int os0 = s_ostep[jr], os1 = s_ostep[jr + 1], om0 = s_omode[jr];
         const float osl0 = s_oslope[jr];
         STAMP(7);
-        const float k1 = eval_body(y, fact_tag);
-        const float k2 = eval_body(y + (dt * k1) * third, fact_tag);
-        const float k3 = eval_body(y + dt * (k2 - k1 * third), fact_tag);
-        const float k4 = eval_body(y + dt * ((k1 - k2) + k3), fact_tag);
+        const float k1 = eval_body(y, fact_tag, prio_tag);
+        const float k2 = eval_body(y + (dt * k1) * third, fact_tag, prio_tag);
+        const float k3 = eval_body(y + dt * (k2 - k1 * third), fact_tag, prio_tag);
+        const float k4 = eval_body(y + dt * ((k1 - k2) + k3), fact_tag, prio_tag);
         const float y1 = y + (((k1 + 3.0f * (k2 + k3)) + k4) * dt) * 0.125f;
         if (os0 == s) {
           // mode / slope as opaque VGPRs: VALU selects instead of scalar branches on the mode
@@ -496,14 +532,30 @@
         }
         STAMP(1);
         y = y1;
+        PROGRESS_STEP(s);
       }
     };
-    if (fact) run(FT{});
-    else run(FF{});
+    if constexpr (SKEW) {
+      // Priority lift (fetode_fused_set_wave_prio): the younger wave runs its
+      // first a.pair[15:8] per cent of the steps with the lifted levels and leads, at twice its partner's
+      // speed; for the rest both stand at the same levels again, the older wave leads and catches up,
+      // and the two end the solve together instead of one running the last third of it alone.
+      const int s_lift = younger ? (int)(((unsigned)a.n_steps * ((unsigned)a.pair >> 8 & 127u) + 50u) / 100u) : 0;
+      if (fact) {
+        if (s_lift > 0) run(FT{}, P1{}, 0, s_lift);
+        run(FT{}, P0{}, s_lift, a.n_steps);
+      } else {
+        if (s_lift > 0) run(FF{}, P1{}, 0, s_lift);
+        run(FF{}, P0{}, s_lift, a.n_steps);
+      }
+    } else {
+      if (fact) run(FT{}, P0{}, 0, a.n_steps);
+      else run(FF{}, P0{}, 0, a.n_steps);
+    }
   } else {
     auto eval = [&](float xin) __attribute__((always_inline)) -> float {
-      if (fact) return eval_body(xin, FT{});
-      return eval_body(xin, FF{});
+      if (fact) return eval_body(xin, FT{}, P0{});
+      return eval_body(xin, FF{}, P0{});
     };
     if constexpr (MP) {
       // ---- the resident dopri5 driver in passes (fetode_dopri5_set_multipass) ----
@@ -518,7 +570,7 @@
       // arithmetic per trajectory, the tape rows, the attempt log and the statuses are the single-pass
       // driver's; the sums are the virtual grid's (grid_sum2_arrive / grid_sum2_poll): bitwise equal.
       auto drive = [&](auto fact_tag) __attribute__((always_inline)) {
-        auto eval = [&](float xin) __attribute__((always_inline)) -> float { return eval_body(xin, fact_tag); };
+        auto eval = [&](float xin) __attribute__((always_inline)) -> float { return eval_body(xin, fact_tag, P0{}); };
         const DopriParams& P = a.dp;
         const double n_el = P.n_total;
         const unsigned G = gridDim.x, VG = (unsigned)P.nblk_global;
@@ -726,7 +778,7 @@
       // one specialised field body, not a runtime choice between two per evaluation
       auto drive = [&](auto fact_tag) __attribute__((always_inline)) {
 #ifndef FETODE_EXP_NO_EVAL
-        auto eval = [&](float xin) __attribute__((always_inline)) -> float { return eval_body(xin, fact_tag); };
+        auto eval = [&](float xin) __attribute__((always_inline)) -> float { return eval_body(xin, fact_tag, P0{}); };
 #else   // diagnostics only: a trivial field, the reductions and control as is
         auto eval = [&](float xin) -> float { return -0.5f * xin; };
 #endif
@@ -903,3 +955,4 @@
     if (act0 && cc0 == 0) a.state[a.B * D + b * H + o0] = prev1;
   }
   STAMP_FLUSH();
+  PROGRESS_FLUSH();

@@ -180,6 +180,23 @@ int64_t fetode_fused_set_v8_range(int64_t lo, int64_t hi);
  * 1 or 2, any other argument changes nothing (so a negative one is a query); returns the previous
  * value.  Process-wide tuning knob. */
 int fetode_fused_set_v8_tpb(int tpb);
+/* Wave skew of the KAN-FET rk4 inference kernel at two trajectories per wave: where the grid holds
+ * more waves than the device has SIMDs (B > 2048 on an MI355X), two waves share each SIMD for the
+ * whole solve; one wave of every such pair sleeps `units` s_sleep units (64 cycles each) once, before
+ * its first step, so that the pair runs a part of an evaluation apart.  Results do not depend on it.
+ * 0 is off (the default); env FETODE_WAVE_SKEW, where anything but a whole number is ignored.  Sets
+ * the value when units >= 0, clamped to s_sleep's range 0..127; a negative argument is a query;
+ * returns the previous value.  Process-wide tuning knob. */
+int fetode_fused_set_wave_skew(int units);
+/* Priority lift of the same kernel, under the same condition: at equal priority a SIMD serves its older
+ * wave, so the younger wave of a pair (the grid's second round of workgroups) runs at half its
+ * partner's speed and ends the solve alone.  With the lift the younger wave runs the first `percent`
+ * per cent of its steps at higher s_setprio levels than the older wave's and leads, the older wave
+ * catches up over the rest, and the two end together.  Results do not depend on it.  Applies where
+ * the grid holds at most two waves per SIMD (2048 < B <= 4096 on an MI355X).  Default 67, 0 is off; env
+ * FETODE_WAVE_PRIO (a whole number 0..100, anything else is ignored).  Sets the value when percent is
+ * 0..100, any other argument is a query; returns the previous value.  Process-wide tuning knob. */
+int fetode_fused_set_wave_prio(int percent);
 /* The current switch points, out[5] = {small_batch_max, tpw1_lo, tpw1_hi, v8_lo, v8_hi} (so a
  * caller can save and restore every knob above). */
 int fetode_fused_get_batch_ranges(int64_t* out);
