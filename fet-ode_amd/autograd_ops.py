@@ -116,10 +116,11 @@ class _KANLinearFn(torch.autograd.Function):
 
 
 def kan_backward(mod, xc, grad, want_x, want_params, gx_accum=None, out=None, entry=None):
-    """HIP VJP of KANLinear: returns (gx, [grad per KAN_PARAM_NAMES or None]).  At the wide-layer
-    widths with 64 / 128 outputs (ETT / ECG fields) the MFMA VJP (fetode_kanlinear_backward_wide);
-    otherwise the generic kernels.  `out`: zero-filled tensors (per KAN_PARAM_NAMES) the parameter
-    gradients are written into instead of fresh ones."""
+    """HIP VJP of KANLinear: returns (gx, [grad per KAN_PARAM_NAMES or None]).  With 64 or 128
+    outputs and any input width the wide layer admits (in >= 16, in % 8 == 0; the ETT / ECG fields
+    among them) the MFMA VJP (fetode_kanlinear_backward_wide); otherwise — other output widths, or no
+    wide plan for the layer — the generic kernels.  `out`: zero-filled tensors (per KAN_PARAM_NAMES)
+    the parameter gradients are written into instead of fresh ones."""
     if mod.out_features in (64, 128) and mod.in_features >= 16 and (want_x or any(want_params)):
         r = _kan_backward_wide(mod, xc, grad, want_x, want_params, gx_accum, out, entry)
         if r is not None:

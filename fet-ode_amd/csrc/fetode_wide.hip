@@ -1795,10 +1795,13 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4))) v
     const float* x0 = el == 0 ? a.y0 : a.xin + pl * BD;
     const float* h0 = a.hs + (int64_t)pl * a.S0 * BH;
     const int64_t nthr = (int64_t)G * kThreads;
-    for (int64_t j = (int64_t)blockIdx.x * kThreads + tid; j < BH; j += nthr) {
-      float v = h0[j];
-      for (int s = 1; s < a.S0; ++s) v = v + h0[s * BH + j];
-      a.st1[j] = v;
+    const int64_t nmem = BH > BD ? BH : BD;   // either layer may be the wider one (D > H: 48 -> 16 -> 48)
+    for (int64_t j = (int64_t)blockIdx.x * kThreads + tid; j < nmem; j += nthr) {
+      if (j < BH) {
+        float v = h0[j];
+        for (int s = 1; s < a.S0; ++s) v = v + h0[s * BH + j];
+        a.st1[j] = v;
+      }
       if (j < BD) a.st0[j] = x0[j];
     }
   }

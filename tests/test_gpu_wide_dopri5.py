@@ -17,6 +17,8 @@ from fet_ode_amd import ett
 from fet_ode_amd.autograd_ops import field_layers
 from fet_ode_amd.dopri5 import ResidentSolve, _Dopri5
 
+from test_wide_shape_family import DOPRI_BATCHES, DOPRI_REFUSED, DOPRI_SHAPES
+
 pytestmark = pytest.mark.gpu
 
 
@@ -84,6 +86,52 @@ def test_wide_resident_dopri5_matches_host_loop(dev, B):
     _compare(host1, res1, f"B={B} first solve")
     _compare(host2, res2, f"B={B} carried state")
     assert len(res1[2]) >= 3
+
+
+# Other admitted width pairs D -> H -> D (tests/test_wide_shape_family.py DOPRI_SHAPES: both layers
+# must be admitted, so D and H are multiples of 16 and every layer is input-sliced at these batches):
+#   (16, 32, 10)   S0 = 2, S1 = 4: single-chunk slices in both layers, layer 1's k from four slabs
+#   (48, 16, 12)   D > H (the hysteresis memory of layer 0 is the longer one); S0 = 2 with 3 chunks
+#                  per slice, S1 = 2; one hidden output block
+#   (16, 144, 10)  nine hidden output blocks; S1 = 2 with 9 chunks per slice
+# B = 1 and a partial second row tile.  The host loop it is compared with runs the layer forward that
+# tests/test_gpu_wide_shapes.py pins to the oracle at these widths.
+@pytest.mark.parametrize("B", DOPRI_BATCHES)
+@pytest.mark.parametrize("D,H,K", DOPRI_SHAPES)
+def test_wide_resident_dopri5_admitted_widths(dev, D, H, K, B):
+    """A first solve and one from the carried state, 239 .. 406 attempts each.  Measured on the MI355X
+    over the six cases: |resident - host| below 5e-4 of the bar (1e-6 of scale) in every solve."""
+    dyn = _dyn(dev, seed=D + H, K=K, latent=D, hidden=H)
+    sd = {k: v.clone() for k, v in dyn.state_dict().items()}
+    z0 = _z0(B, dev, D=D)
+    t = torch.linspace(0.0, 3.0, steps=4, device=dev)
+    kw = dict(rtol=1e-3, atol=1e-4)
+    host1 = _solve(dyn, z0, t, False, **kw)
+    host2 = _solve(dyn, z0 * 0.9, t, False, **kw)
+    dyn = _dyn(dev, seed=D + H, K=K, latent=D, hidden=H)
+    dyn.load_state_dict(sd)
+    res1 = _solve(dyn, z0, t, True, **kw)
+    res2 = _solve(dyn, z0 * 0.9, t, True, **kw)
+    e1 = _compare(host1, res1, f"({D}, {H}, {K}) B={B} first solve")
+    e2 = _compare(host2, res2, f"({D}, {H}, {K}) B={B} carried state")
+    print(f"resident ({D},{H},{K}) B={B}: {len(res1[2])} + {len(res2[2])} attempts, err / 1e-6 scale {e1 / 1e-6:.3f} {e2 / 1e-6:.3f}")
+    assert len(res1[2]) >= 3
+
+
+@pytest.mark.parametrize("D,H,K", DOPRI_REFUSED)
+def test_wide_resident_dopri5_refused_pairs_take_host_loop(dev, D, H, K):
+    """D = 24 / 40: layer 1 (H -> D) has no wide kernel (D % 16 != 0), so the solve is the host loop
+    — by dispatch, not by error — and finite."""
+    dyn = _dyn(dev, seed=D + H, K=K, latent=D, hidden=H)
+    prev = F.dopri5.set_wide_resident_dopri5(True, gap=(0, 0))
+    try:
+        with torch.no_grad():
+            sol = F.odeint(dyn, _z0(100, dev, D=D), torch.linspace(0.0, 1.0, steps=3, device=dev), method="dopri5",
+                           rtol=1e-3, atol=1e-4)
+    finally:
+        F.dopri5.set_wide_resident_dopri5(prev, gap=(512, 8192))
+    assert isinstance(F.dopri5.dopri5_solve.last, _Dopri5)
+    assert sol.shape == (3, 100, D) and torch.isfinite(sol).all()
 
 
 def test_wide_resident_dopri5_reference_defaults_and_first_step(dev):
