@@ -29,6 +29,7 @@
 //                       dbias = coef G_o, dcoef = Ps A + bias G_o
 //   KAN (o,i):          base = sum g_o SiLU(x_i), spline_c = sum g_o B_c(x_i)
 //   logistic (o,i,j):   sum g_o sigmoid_ij;  a_ij, b_ij directly.
+#include <algorithm>
 #include <cstdlib>
 #include <cstring>
 #include <type_traits>
@@ -640,34 +641,46 @@ struct BwdEntry {
                                // recorded adjoints (then ks), or every sum in the sweep; or null
   bwd_fn ks;                   // the KAN sums over all samples after v7 (kansum_kernel)
 };
+// One table row: every kernel of a [D, H, D] shape, each a function of <D, H, K, NB, NG, FERRO> alone.  KK
+// is the kernels' element count, TPW the trajectories per wave of the one-kernel sweep; a new kernel
+// variant is one member above and one assignment here.
+template <int D, int H, int K, int KK, int NB, int NG, bool FERRO, int TPW>
+BwdEntry bwd_entry() {
+  BwdEntry e{};
+  e.D = D, e.H = H, e.K = K, e.NB = NB, e.NG = NG;
+  e.ferro = FERRO;
+  e.tpw = TPW;
+  e.fn = fixed_bwd_kernel<D, H, KK, NB, NG, FERRO, true, TPW>;
+  e.dopri = dopri_bwd_kernel<D, H, KK, NB, NG, FERRO, 2>;
+  e.dtpw = 2;
+  e.dopri1 = dopri_bwd_kernel<D, H, KK, NB, NG, FERRO, 1>;
+  if constexpr (TPW > 1) e.fn1 = fixed_bwd_kernel<D, H, KK, NB, NG, FERRO, true, 1>;
+  if constexpr (FERRO) {   // the KAN-FET sweep's alternatives
+#ifdef FETODE_DIAG   // the split structure (measured slower) lives in the diagnostic build only
+    e.adj = fixed_bwd_kernel<D, H, KK, NB, NG, FERRO, false, 1>;
+    e.sum0 = param_sum_kernel<D, H, KK, NB, NG, 0>;
+    e.sum1 = param_sum_kernel<D, H, KK, NB, NG, 1>;
+#endif
+    e.v7 = sweep7_kernel<false>;
+    e.v7s = sweep7_kernel<true>;
+    e.ks = kansum_kernel;
+  }
+  return e;
+}
 const BwdEntry kBwd[] = {
     // LV KAN-FET [2,10,2]: one kernel, two trajectories per wave (measured: TPW 1 / 2 / 4 = 1034 / 897 /
     // 1203 us at B = 4096); the split structure as the alternative
-#ifdef FETODE_DIAG   // the split structure (measured slower) lives in the diagnostic build only
-    {2, 10, 10, 10, 12, true, 2, fixed_bwd_kernel<2, 10, 10, 10, 12, true, true, 2>,
-     fixed_bwd_kernel<2, 10, 10, 10, 12, true, false, 1>, param_sum_kernel<2, 10, 10, 10, 12, 0>,
-     param_sum_kernel<2, 10, 10, 10, 12, 1>, dopri_bwd_kernel<2, 10, 10, 10, 12, true, 2>, 2,
-     dopri_bwd_kernel<2, 10, 10, 10, 12, true, 1>, fixed_bwd_kernel<2, 10, 10, 10, 12, true, true, 1>,
-#else
-    {2, 10, 10, 10, 12, true, 2, fixed_bwd_kernel<2, 10, 10, 10, 12, true, true, 2>, nullptr, nullptr, nullptr,
-     dopri_bwd_kernel<2, 10, 10, 10, 12, true, 2>, 2, dopri_bwd_kernel<2, 10, 10, 10, 12, true, 1>,
-     fixed_bwd_kernel<2, 10, 10, 10, 12, true, true, 1>,
-#endif
-     sweep7_kernel<false>, sweep7_kernel<true>, kansum_kernel},
-    // LV KAN [2,10,2] (126 VGPRs: four waves per SIMD already)
-    {2, 10, 0, 10, 12, false, 1, fixed_bwd_kernel<2, 10, 1, 10, 12, false, true, 1>, nullptr, nullptr, nullptr,
-     dopri_bwd_kernel<2, 10, 1, 10, 12, false, 2>, 2, dopri_bwd_kernel<2, 10, 1, 10, 12, false, 1>, nullptr,
-     nullptr, nullptr, nullptr},
+    bwd_entry<2, 10, 10, 10, 10, 12, true, 2>(),
+    // LV KAN [2,10,2] (126 VGPRs: four waves per SIMD already): the entry's K is 0, the kernels are
+    // instantiated at K = 1 (unused without Ferro: their K is 0)
+    bwd_entry<2, 10, 0, 1, 10, 12, false, 1>(),
 };
 // Which path the KAN-FET sweep takes (fetode_backward_set_split; env FETODE_BWD_SPLIT).  Default:
 // the one-kernel sweep — measured on MI355X at B = 4096, rk4, 34 steps: one kernel 1.06 ms vs the
 // split 0.69 (adjoint sweep) + 0.25 + 0.31 (layer sums) ms (profiles/r02_split_pmc.txt).
 int g_bwd_split = -1;
 bool use_split(const BwdEntry* e) {
-  if (g_bwd_split < 0) {
-    const char* v = getenv("FETODE_BWD_SPLIT");
-    g_bwd_split = v ? atoi(v) != 0 : 0;
-  }
+  if (g_bwd_split < 0) g_bwd_split = env_int("FETODE_BWD_SPLIT", 0) != 0;
   return e->adj && g_bwd_split != 0;
 }
 constexpr int64_t kSumBlocks = 1024;  // param_sum_kernel blocks per layer (= partial rows)
@@ -680,10 +693,7 @@ constexpr int64_t kSumBlocks = 1024;  // param_sum_kernel blocks per layer (= pa
 int g_bwd_v7 = -1;
 int g_bwd_tpw = 0;  // fetode_backward_set_tpw
 int v7_mode() {
-  if (g_bwd_v7 < 0) {
-    const char* v = getenv("FETODE_BWD_V7");
-    g_bwd_v7 = v ? atoi(v) : 1;
-  }
+  if (g_bwd_v7 < 0) g_bwd_v7 = (int)env_int("FETODE_BWD_V7", 1);
   return g_bwd_v7;
 }
 int64_t n_evals_of(int32_t method, int32_t n_steps) {
@@ -790,15 +800,8 @@ int fixed_tpw(const BwdEntry* e, int64_t B) {
   if (!e->fn1) return e->tpw;
   if (g_bwd_tpw == 1) return 1;
   if (g_bwd_tpw == 2) return e->tpw;
-  static int64_t cap = -1;
-  if (cap < 0 && getenv("FETODE_BWD_TPW1") && atoi(getenv("FETODE_BWD_TPW1")) == 0) cap = 0;  // A/B knob
-  if (cap < 0) {
-    int dev = 0, n_cu = 0, per = 0;
-    cap = (hipGetDevice(&dev) == hipSuccess &&
-           hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess &&
-           hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, e->fn1, 64 * kTPB, 0) == hipSuccess)
-              ? (int64_t)per * n_cu * kTPB : 0;
-  }
+  static const bool on = env_int("FETODE_BWD_TPW1", 1) != 0;  // A/B knob
+  const int64_t cap = on ? std::max<int64_t>(resident_wgs(e->fn1, 64 * kTPB), 0) * kTPB : 0;  // resident waves
   // measured (tools/diag/bwd_small_time.py, rk4 iteration): B = 512 0.73 vs 0.93 ms, B = 2048 0.79 vs
   // 0.75 ms — one trajectory per wave while at most half the resident waves are needed
   return 2 * B <= cap ? 1 : e->tpw;
@@ -870,8 +873,7 @@ int fetode_integrate_fixed_backward(const fetode_field_t* f, const void* plan, i
   BwdArgs a;
   memset(&a, 0, sizeof(a));
   a.plan = (const float*)plan;
-  layer_plan(f->kan[0], f->ferro ? &f->ferro[0] : nullptr, 0, &a.P0);
-  layer_plan(f->kan[1], f->ferro ? &f->ferro[1] : nullptr, a.P0.end, &a.P1);
+  field_plans(f, &a.P0, &a.P1);
   a.k0 = f->kan[0];
   a.k1 = f->kan[1];
   if (f->ferro) {
@@ -936,18 +938,7 @@ int fetode_integrate_fixed_backward(const fetode_field_t* f, const void* plan, i
 // ---- reverse sweep of the resident dopri5 solve ----
 // every workgroup resident at once (one grid sum per attempt): the occupancy of the kernel
 static int64_t dopri_bwd_resident_wgs(const BwdEntry* e, bool one = false) {
-  static int n_cu = 0;
-  static int per_cu[2][2] = {{0, 0}, {0, 0}};
-  const int fi = e->ferro ? 0 : 1, v = one ? 1 : 0;
-  if (!n_cu) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      return -1;
-  }
-  if (!per_cu[fi][v] &&
-      hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu[fi][v], one ? e->dopri1 : e->dopri, 64 * kTPB, 0) != hipSuccess)
-    return -1;
-  return (int64_t)per_cu[fi][v] * n_cu;
+  return resident_wgs(one ? e->dopri1 : e->dopri, 64 * kTPB);
 }
 // fetode_integrate_dopri5_backward_set_shape: 0 automatic, 1 / 2 trajectories per wave
 static int g_dopri_bwd_shape = 0;
@@ -1078,8 +1069,7 @@ int fetode_integrate_dopri5_backward(const fetode_field_t* f, const void* plan, 
   memset(&d, 0, sizeof(d));
   BwdArgs& a = d.b;
   a.plan = (const float*)plan;
-  layer_plan(f->kan[0], f->ferro ? &f->ferro[0] : nullptr, 0, &a.P0);
-  layer_plan(f->kan[1], f->ferro ? &f->ferro[1] : nullptr, a.P0.end, &a.P1);
+  field_plans(f, &a.P0, &a.P1);
   a.k0 = f->kan[0];
   a.k1 = f->kan[1];
   if (f->ferro) {

@@ -38,17 +38,7 @@ constexpr int kMpWords[2] = {BReg<BL<2, 10, 10, 10, 12, true>>::NW + BReg<BL<10,
 
 namespace fetode {
 
-int64_t dopri_bwd_mp_resident_wgs(bool ferro) {
-  static int n_cu = 0, per_cu[2] = {0, 0};
-  const int fi = ferro ? 0 : 1;
-  if (!n_cu) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      return -1;
-  }
-  if (!per_cu[fi] && hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu[fi], kMpFn[fi], 64 * kTPB, 0) != hipSuccess) return -1;
-  return (int64_t)per_cu[fi] * n_cu;
-}
+int64_t dopri_bwd_mp_resident_wgs(bool ferro) { return resident_wgs(kMpFn[ferro ? 0 : 1], 64 * kTPB); }
 
 // the parking area of `vgrid` virtual workgroups: per virtual wave its 2 x 2 element records and
 // its gradient-sum registers, lane-contiguous

@@ -48,7 +48,27 @@ struct LayerPlan {
 };
 
 void layer_plan(const fetode_kanlinear_t& kl, const fetode_ferro_t* fl, int64_t base, LayerPlan* p);
+// both layers' plans of a depth-2 field, layer 1 packed behind layer 0
+inline void field_plans(const fetode_field_t* f, LayerPlan* P0, LayerPlan* P1) {
+  layer_plan(f->kan[0], f->ferro ? &f->ferro[0] : nullptr, 0, P0);
+  layer_plan(f->kan[1], f->ferro ? &f->ferro[1] : nullptr, P0->end, P1);
+}
 int validate_field(const fetode_field_t* f);
+
+// An integer knob of the environment: `dflt` when `name` is unset, else its value read as atoll does.
+int64_t env_int(const char* name, int64_t dflt);
+double env_float(const char* name, double dflt);
+
+// How many workgroups of a kernel the current device holds at once: what every device-resident
+// solver and sweep sizes its grid by.  Cached per (device, kernel, threads, dynamic LDS bytes) behind
+// one lock, so a repeat call costs hipGetDevice and a lookup; a failed query is not cached.
+int device_cus();                                                       // 0: query failed
+int occupancy_per_cu(const void* fn, int threads, size_t lds = 0);     // -1: query failed
+int64_t resident_wgs(const void* fn, int threads, size_t lds = 0);     // per CU x device_cus(); -1: query failed
+template <class... A>
+int64_t resident_wgs(void (*fn)(A...), int threads, size_t lds = 0) {
+  return resident_wgs(reinterpret_cast<const void*>(fn), threads, lds);
+}
 // The lane-ordered image block of fields with a specialised fused kernel (fetode_fused4_image.h,
 // fetode_fused.hip): its size in floats (0: no fused kernel for the field, no block), and its build
 // from the classic sections already enqueued on `stream`; img: the block's float offset in the plan

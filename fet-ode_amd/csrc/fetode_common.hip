@@ -4,7 +4,10 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <map>
+#include <mutex>
 #include <string>
+#include <tuple>
 
 #include "fetode_common.h"
 
@@ -12,26 +15,72 @@ namespace fetode {
 
 static thread_local std::string g_last_error;
 
+int64_t env_int(const char* name, int64_t dflt) {
+  const char* v = getenv(name);
+  return v ? (int64_t)atoll(v) : dflt;
+}
+double env_float(const char* name, double dflt) {
+  const char* v = getenv(name);
+  return v ? atof(v) : dflt;
+}
+
 // -1: not yet read from the environment
 int g_resident_mode = -1;
 int resident_mode() {
-  if (g_resident_mode < 0) {
-    const char* v = getenv("FETODE_COOPERATIVE");
-    g_resident_mode = v && atoi(v) != 0;
-  }
+  if (g_resident_mode < 0) g_resident_mode = env_int("FETODE_COOPERATIVE", 0) != 0;
   return g_resident_mode;
 }
 
 int g_dp_multipass = -1;
 int64_t g_dp_grid_limit = 0;
 int dp_multipass() {
-  if (g_dp_multipass < 0) {
-    const char* v = getenv("FETODE_DOPRI5_MULTIPASS");
-    g_dp_multipass = v && atoi(v) != 0;
-  }
+  if (g_dp_multipass < 0) g_dp_multipass = env_int("FETODE_DOPRI5_MULTIPASS", 0) != 0;
   return g_dp_multipass;
 }
 int64_t dp_grid_limit() { return dp_multipass() ? g_dp_grid_limit : 0; }
+
+namespace {
+struct CapacityCache {
+  std::mutex mu;
+  std::map<int, int> cus;                                             // device -> CU count
+  std::map<std::tuple<int, const void*, int, size_t>, int> per_cu;  // (device, kernel, threads, LDS) -> workgroups
+};
+CapacityCache& capacity_cache() {
+  static CapacityCache c;
+  return c;
+}
+}  // namespace
+
+int device_cus() {
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return 0;
+  CapacityCache& c = capacity_cache();
+  std::lock_guard<std::mutex> lock(c.mu);
+  const auto it = c.cus.find(dev);
+  if (it != c.cus.end()) return it->second;
+  int n = 0;
+  if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) return 0;
+  return c.cus[dev] = n;
+}
+
+int occupancy_per_cu(const void* fn, int threads, size_t lds) {
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return -1;
+  CapacityCache& c = capacity_cache();
+  std::lock_guard<std::mutex> lock(c.mu);
+  const auto key = std::make_tuple(dev, fn, threads, lds);
+  const auto it = c.per_cu.find(key);
+  if (it != c.per_cu.end()) return it->second;
+  int n = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, fn, threads, lds) != hipSuccess || n < 0) return -1;
+  return c.per_cu[key] = n;
+}
+
+int64_t resident_wgs(const void* fn, int threads, size_t lds) {
+  const int n_cu = device_cus();
+  const int per_cu = n_cu > 0 ? occupancy_per_cu(fn, threads, lds) : -1;
+  return per_cu < 0 ? -1 : (int64_t)per_cu * n_cu;
+}
 
 hipError_t resident_launch(const void* fn, dim3 grid, dim3 block, void** args, size_t lds, hipStream_t s) {
   if (resident_mode()) return hipLaunchCooperativeKernel(fn, grid, block, args, (unsigned)lds, s);

@@ -712,19 +712,14 @@ int ecg_dopri5_impl(const fetode_hlogistic_t* layer, const float* wT, const floa
   a.tape = tape;
   a.tape_cap = taped ? tape_cap : 0;
   a.init_rec = init_rec;
-  // per-variant launch facts, queried once (static LDS, the dynamic-LDS cap) and per LDS size
-  // (occupancy): the launch path does no runtime queries on repeat calls
-  static int n_cu_of[64] = {0};
+  // per-variant launch facts, queried once (static LDS, the dynamic-LDS cap; the occupancy per LDS
+  // size is occupancy_per_cu's cache): the launch path does no runtime queries on repeat calls
   static struct {
     int static_lds = -1;
     size_t lds = 0;
-    int per_cu = 0;
   } vstate_all[2][kNumEcgVariants];
-  int dev = 0;
-  HIP_CHECK_RET(hipGetDevice(&dev));
-  if (dev < 0 || dev >= 64) return set_err(FETODE_EINVAL, "ecg dopri5: device %d", dev);
-  if (!n_cu_of[dev]) HIP_CHECK_RET(hipDeviceGetAttribute(&n_cu_of[dev], hipDeviceAttributeMultiprocessorCount, dev));
-  const int n_cu = n_cu_of[dev];
+  const int n_cu = device_cus();
+  if (n_cu <= 0) return set_err(FETODE_EHIP, "ecg dopri5: no device");
   a.PS = head_part(F);
   // the smallest workgroup whose grid is co-resident (one cooperative grid) and whose head
   // weight fits LDS + its register tail
@@ -744,16 +739,15 @@ int ecg_dopri5_impl(const fetode_hlogistic_t* layer, const float* wT, const floa
     const int QL = (int)std::min<int64_t>(a.PS, (w_floats / ((int64_t)kHeadParts * 64)) & ~(int64_t)3);
     if (a.PS - QL > v.tail) continue;
     const size_t lds = (size_t)kHeadParts * QL * 64 * sizeof(float) + (size_t)(prm_bytes + phi_bytes);
-    if (vs.lds != lds) {
+    if (vs.lds != lds) {  // before the occupancy query of a new LDS size
       HIP_CHECK_RET(hipFuncSetAttribute(v.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      int per_cu = 0;
-      HIP_CHECK_RET(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, v.fn, kResThreads, lds));
       vs.lds = lds;
-      vs.per_cu = per_cu;
     }
+    const int api_per_cu = occupancy_per_cu(v.fn, kResThreads, lds);
+    if (api_per_cu < 0) return set_err(FETODE_EHIP, "ecg dopri5: occupancy query failed");
     const int64_t grid = (B + v.rows - 2) / (v.rows - 1);
     // one workgroup per CU below the API's answer when it admits several (it can be one too high)
-    const int per_cu = vs.per_cu > 1 ? vs.per_cu - 1 : vs.per_cu;
+    const int per_cu = api_per_cu > 1 ? api_per_cu - 1 : api_per_cu;
     if (per_cu <= 0 || grid > (int64_t)per_cu * n_cu) continue;
     a.QL = QL;
     hipStream_t s = (hipStream_t)stream;

@@ -630,22 +630,11 @@ size_t bwd_lds(int F) { return sizeof(float) * (size_t)(4 * F + kBwdRows * ((F +
 
 // the most workgroups of the sweep that are resident at once (0: none, < 0: no device)
 int64_t bwd_max_grid(int F) {
-  static int n_cu_of[64] = {0};
-  static int per_cu_of[kMaxF + 1] = {0};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return -1;
-  if (!n_cu_of[dev] &&
-      hipDeviceGetAttribute(&n_cu_of[dev], hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-    return -1;
-  if (!per_cu_of[F]) {
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(ecg_dopri5_bwd_kernel),
-                                                     kBwdThreads, bwd_lds(F)) != hipSuccess)
-      return -1;
-    // one workgroup per CU below the API's answer when it admits several (it can be one too high)
-    per_cu_of[F] = per_cu > 1 ? per_cu - 1 : (per_cu == 1 ? 1 : -1);
-  }
-  return per_cu_of[F] < 0 ? 0 : (int64_t)per_cu_of[F] * n_cu_of[dev];
+  const int n_cu = device_cus();
+  const int per_cu = n_cu > 0 ? occupancy_per_cu(reinterpret_cast<const void*>(ecg_dopri5_bwd_kernel), kBwdThreads, bwd_lds(F)) : -1;
+  if (per_cu < 0) return -1;
+  // one workgroup per CU below the API's answer when it admits several (it can be one too high)
+  return (int64_t)(per_cu > 1 ? per_cu - 1 : per_cu) * n_cu;
 }
 
 int check_shape(const fetode_hlogistic_t* layer, const char* what) {

@@ -674,20 +674,10 @@ bool any_ferro(const fetode_ferro_grad_t& g) { return g.k || g.Ec || g.Ps || g.b
 // ---- dopri5 ----
 static int64_t fieldn_dopri_grid(int64_t B) { return (B + kFbWaves - 1) / kFbWaves; }
 
-static int64_t fieldn_dopri_resident(bool ferro) {
-  static int n_cu = 0, per_cu[2] = {0, 0};
-  const int fi = ferro ? 0 : 1;
-  if (!n_cu) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      return -1;
-  }
-  if (!per_cu[fi] && hipOccupancyMaxActiveBlocksPerMultiprocessor(
-                         &per_cu[fi], ferro ? (const void*)fieldn_dopri_bwd_kernel<true> : (const void*)fieldn_dopri_bwd_kernel<false>,
-                         64 * kFbWaves, 0) != hipSuccess)
-    return -1;
-  return (int64_t)per_cu[fi] * n_cu;
+static const void* fieldn_dopri_bwd_fn(bool ferro) {
+  return ferro ? (const void*)fieldn_dopri_bwd_kernel<true> : (const void*)fieldn_dopri_bwd_kernel<false>;
 }
+static int64_t fieldn_dopri_resident(bool ferro) { return resident_wgs(fieldn_dopri_bwd_fn(ferro), 64 * kFbWaves); }
 
 // workspace: grid-sum words and slots | output / hidden adjoint planes | layer-input planes | KAN VJP scratch
 // the parameter-VJP scratch: the larger KANLinear workspace, or the Ferro row-split partials
@@ -763,8 +753,7 @@ int fetode::fieldn_fixed_backward(const fetode_field_t* f, const void* plan, int
   FbArgs a;
   memset(&a, 0, sizeof(a));
   a.plan = (const float*)plan;
-  layer_plan(f->kan[0], f->ferro ? &f->ferro[0] : nullptr, 0, &a.P0);
-  layer_plan(f->kan[1], f->ferro ? &f->ferro[1] : nullptr, a.P0.end, &a.P1);
+  field_plans(f, &a.P0, &a.P1);
   a.method = method;
   a.B = B;
   a.step_coef = step_coef;
@@ -781,10 +770,8 @@ int fetode::fieldn_fixed_backward(const fetode_field_t* f, const void* plan, int
   a.gadj = gadj;
   const int64_t pbytes = (int64_t)sizeof(float) * a.P1.end;
   const int tpw = 64 / fb_lanes_per_traj(D, H);
-  static const int lds_on = [] {  // FETODE_FIELDN_LDS=0: the plan read from global memory (A/B)
-    const char* e = getenv("FETODE_FIELDN_LDS");
-    return e ? atoi(e) : 1;
-  }();
+  // FETODE_FIELDN_LDS=0: the plan read from global memory (A/B)
+  static const int lds_on = (int)env_int("FETODE_FIELDN_LDS", 1);
   if (lds_on && pbytes <= kFbLdsMax) {
     auto* kfn = f->ferro ? fieldn_adj_kernel<true, true> : fieldn_adj_kernel<false, true>;
     static bool attr[2] = {false, false};  // dynamic LDS beyond the 64 KB default
@@ -837,8 +824,7 @@ int fetode::fieldn_dopri5_backward(const fetode_field_t* f, const void* plan, in
   memset(&d, 0, sizeof(d));
   FbArgs& a = d.b;
   a.plan = (const float*)plan;
-  layer_plan(f->kan[0], f->ferro ? &f->ferro[0] : nullptr, 0, &a.P0);
-  layer_plan(f->kan[1], f->ferro ? &f->ferro[1] : nullptr, a.P0.end, &a.P1);
+  field_plans(f, &a.P0, &a.P1);
   a.B = B;
   a.T = T;
   a.gsol = grad_solution;
@@ -872,8 +858,7 @@ int fetode::fieldn_dopri5_backward(const fetode_field_t* f, const void* plan, in
   d.status = status;
   HIP_CHECK_RET(hipMemsetAsync(workspace, 0, sizeof(unsigned) * kDpBarWords, s));
   void* args[] = {&d};
-  HIP_CHECK_RET(resident_launch(f->ferro ? (const void*)fieldn_dopri_bwd_kernel<true> : (const void*)fieldn_dopri_bwd_kernel<false>,
-                                dim3((unsigned)grid), dim3(64 * kFbWaves), args, 0, s));
+  HIP_CHECK_RET(resident_launch(fieldn_dopri_bwd_fn(f->ferro != nullptr), dim3((unsigned)grid), dim3(64 * kFbWaves), args, 0, s));
   if (n_ev == 0) return zero_grads(f, kan_grads, ferro_grads, s);
   const int64_t R = (int64_t)n_ev * B;
   return fieldn_param_vjps(f, B, n_ev, d.Xc, d.Hc, a.gadj, a.gadj + R * D, state0, a.init_mask, kan_grads,

@@ -1417,68 +1417,66 @@ struct FusedEntry {
   int img_floats;                    // the plan's image block (fetode_fused4_image.h)
   void (*img_fn)(LayerPlan, LayerPlan, float*, int64_t);
 };
+// One table row: every kernel of a [2, H, 2] shape, each a function of <H, K, NB, NG, FERRO> alone.  K_ is
+// the kernels' element count and KI the image's; a new kernel variant is one member above and one
+// assignment here.
+template <int H, int K, int K_, int KI, int NB, int NG, bool FERRO>
+FusedEntry fused_entry() {
+  FusedEntry e{};
+  e.in0 = 2, e.h = H, e.out = 2, e.K = K, e.NB = NB, e.NG = NG;
+  e.ferro = FERRO;
+  e.fn = fused4_kernel<H, K_, NB, NG, FERRO, false>;
+  e.fn_rk4 = fused4_kernel<H, K_, NB, NG, FERRO, true>;
+  e.small = small6_kernel<FERRO, false>;
+  e.small_rk4 = small6_kernel<FERRO, true>;
+  e.dopri = fused4_kernel<H, K_, NB, NG, FERRO, false, true>;
+  e.dopri_tape = fused4_kernel<H, K_, NB, NG, FERRO, false, true, true>;
+  e.small_dopri = small6_kernel<FERRO, false, true, false>;
+  e.small_dopri_tape = small6_kernel<FERRO, false, true, true>;
+  e.small_tape = small6_kernel<FERRO, false, false, true>;
+  e.small_rk4_tape = small6_kernel<FERRO, true, false, true>;
+  e.fn_rk4_1 = fused4_kernel<H, K_, NB, NG, FERRO, true, false, false, 1>;
+  e.rk4_v8 = v8_kernel<FERRO, 1>;
+  e.rk4_v8x2 = v8_kernel<FERRO, 2>;
+  e.fn_tape = fused4_kernel<H, K_, NB, NG, FERRO, false, false, true>;
+  e.fn_rk4_tape = fused4_kernel<H, K_, NB, NG, FERRO, true, false, true>;
+  e.fn_rk4_1_tape = fused4_kernel<H, K_, NB, NG, FERRO, true, false, true, 1>;
+  e.dopri_mp = fused4_mp_kernel<H, K_, NB, NG, FERRO, false>;
+  e.dopri_mp_tape = fused4_mp_kernel<H, K_, NB, NG, FERRO, true>;
+  e.img_floats = Fused4Block<H, KI, NB, NG>::NF;
+  e.img_fn = fused_image_kernel<H, KI, NB, NG>;
+  return e;
+}
 const FusedEntry kFused[] = {
     // LV KAN-FET [2,10,2], K=10 (train_kanfet_node_predprey.py:146)
-    {2, 10, 2, 10, 10, 12, true, fused4_kernel<10, 10, 10, 12, true, false>, fused4_kernel<10, 10, 10, 12, true, true>,
-     small6_kernel<true, false>, small6_kernel<true, true>, fused4_kernel<10, 10, 10, 12, true, false, true>,
-     fused4_kernel<10, 10, 10, 12, true, false, true, true>, small6_kernel<true, false, true, false>,
-     small6_kernel<true, false, true, true>, small6_kernel<true, false, false, true>,
-     small6_kernel<true, true, false, true>, fused4_kernel<10, 10, 10, 12, true, true, false, false, 1>,
-     v8_kernel<true, 1>, v8_kernel<true, 2>, fused4_kernel<10, 10, 10, 12, true, false, false, true>,
-     fused4_kernel<10, 10, 10, 12, true, true, false, true>, fused4_kernel<10, 10, 10, 12, true, true, false, true, 1>,
-     fused4_mp_kernel<10, 10, 10, 12, true, false>, fused4_mp_kernel<10, 10, 10, 12, true, true>,
-     Fused4Block<10, 10, 10, 12>::NF, fused_image_kernel<10, 10, 10, 12>},
-    // LV KAN [2,10,2] (predator_prey.py:101)
-    {2, 10, 2, 1, 10, 12, false, fused4_kernel<10, 2, 10, 12, false, false>, fused4_kernel<10, 2, 10, 12, false, true>,
-     small6_kernel<false, false>, small6_kernel<false, true>, fused4_kernel<10, 2, 10, 12, false, false, true>,
-     fused4_kernel<10, 2, 10, 12, false, false, true, true>, small6_kernel<false, false, true, false>,
-     small6_kernel<false, false, true, true>, small6_kernel<false, false, false, true>,
-     small6_kernel<false, true, false, true>, fused4_kernel<10, 2, 10, 12, false, true, false, false, 1>,
-     v8_kernel<false, 1>, v8_kernel<false, 2>, fused4_kernel<10, 2, 10, 12, false, false, false, true>,
-     fused4_kernel<10, 2, 10, 12, false, true, false, true>, fused4_kernel<10, 2, 10, 12, false, true, false, true, 1>,
-     fused4_mp_kernel<10, 2, 10, 12, false, false>, fused4_mp_kernel<10, 2, 10, 12, false, true>,
-     Fused4Block<10, 0, 10, 12>::NF, fused_image_kernel<10, 0, 10, 12>},
+    fused_entry<10, 10, 10, 10, 10, 12, true>(),
+    // LV KAN [2,10,2] (predator_prey.py:101): the entry's K is 1, the kernels are instantiated at K_ = 2
+    // (unused without Ferro: their K is 0) and the image block at no elements, K = 0
+    fused_entry<10, 1, 2, 0, 10, 12, false>(),
 };
 
 // Batches up to kSmallMax take v6 (one trajectory per 3-wave workgroup, latency-bound chain split
 // over 160 lanes), larger ones v4 (two trajectories per wave, issue-bound); training tapes are v4
 // only.  FETODE_SMALL_MAX overrides the switch point (diagnostics / tuning).
-int64_t g_small_max = [] {
-  const char* e = getenv("FETODE_SMALL_MAX");
-  return e ? (int64_t)atoll(e) : (int64_t)512;  // measured switch point (tools/diag/batch_sweep.py)
-}();
+int64_t g_small_max = env_int("FETODE_SMALL_MAX", 512);  // measured switch point (tools/diag/batch_sweep.py)
 int64_t small_max() { return g_small_max; }
 // Inference rk4 batches in (g_tpw1_lo, g_tpw1_hi] take v7 at one trajectory per wave (before the
 // v6 / v4 choice; env FETODE_TPW1_LO / FETODE_TPW1_HI).  Measured (tools/diag/batch_sweep.py,
 // profiles/r05_t1w_sweep*.log, us per 34-step solve, v6 / one / two per wave): B = 256 77 / 93 / 114,
 // 384 98 / 97 / 114,
 // 512 101 / 97 / 113, 768 129 / 97 / 119, 1024 146 / 99 / 119, 1536 202 / 133 / 117.
-int64_t g_tpw1_lo = [] {
-  const char* e = getenv("FETODE_TPW1_LO");
-  return e ? (int64_t)atoll(e) : (int64_t)320;
-}();
-int64_t g_tpw1_hi = [] {
-  const char* e = getenv("FETODE_TPW1_HI");
-  return e ? (int64_t)atoll(e) : (int64_t)1024;
-}();
+int64_t g_tpw1_lo = env_int("FETODE_TPW1_LO", 320);
+int64_t g_tpw1_hi = env_int("FETODE_TPW1_HI", 1024);
 // Inference rk4 batches in (g_v8_lo, g_v8_hi] take v8 (two waves per trajectory), before every other
 // choice (env FETODE_V8_LO / FETODE_V8_HI).
 // Measured (tools/diag/batch_sweep.py, profiles/r06_v8_sweep.log, us per 34-step solve, v6 / v7 one
 // per wave / v8 at two trajectories per four-wave workgroup): B = 256 77 / 93 / 84, 320 94 / 92 / 84,
 // 448 96 / 93 / 84, 512 97 / 93 / 85, 576 124 / 93 / 112 (v8 past one wave per SIMD), 1024 140 / 98 / 112.
-int64_t g_v8_lo = [] {
-  const char* e = getenv("FETODE_V8_LO");
-  return e ? (int64_t)atoll(e) : (int64_t)256;
-}();
-int64_t g_v8_hi = [] {
-  const char* e = getenv("FETODE_V8_HI");
-  return e ? (int64_t)atoll(e) : (int64_t)512;
-}();
-int g_v8_tpb = [] {   // trajectories per v8 workgroup (1: two waves, 2: four waves); env FETODE_V8_TPB
-  const char* e = getenv("FETODE_V8_TPB");
-  const int v = e ? atoi(e) : 2;
-  return v == 1 || v == 2 ? v : 2;   // anything else is ignored: the default stays
-}();
+int64_t g_v8_lo = env_int("FETODE_V8_LO", 256);
+int64_t g_v8_hi = env_int("FETODE_V8_HI", 512);
+// trajectories per v8 workgroup (1: two waves, 2: four waves); env FETODE_V8_TPB, where anything else
+// is ignored: the default stays
+int g_v8_tpb = (int)env_int("FETODE_V8_TPB", 2) == 1 ? 1 : 2;
 // Wave skew of the headline rk4 kernel (fused4 body): s_sleep units (64 cycles
 // each) one wave of every SIMD pair sleeps before its first step; 0: off.  env FETODE_WAVE_SKEW, where
 // anything but a whole number is ignored and a number is clamped to s_sleep's range.
@@ -1882,10 +1880,8 @@ __global__ __launch_bounds__(DOPRI ? 64 : (LDSP ? 64 * kFnWavesL : 64 * kFnWaves
 
 // the shapes fieldn serves (any other depth-2 [D, H, D] field of the fused kernels' basis shape)
 bool fieldn_supported(const fetode_field_t* f) {
-  static const bool on = [] {  // FETODE_FIELDN=0: these shapes take the per-stage path (A/B diagnostics)
-    const char* e = getenv("FETODE_FIELDN");
-    return !e || atoi(e) != 0;
-  }();
+  // FETODE_FIELDN=0: these shapes take the per-stage path (A/B diagnostics)
+  static const bool on = env_int("FETODE_FIELDN", 1) != 0;
   if (!on || f->n_layers != 2) return false;
   const fetode_kanlinear_t &k0 = f->kan[0], &k1 = f->kan[1];
   if (k0.in_features < 1 || k0.in_features > kFnMaxD || k1.out_features != k0.in_features ||
@@ -1896,20 +1892,26 @@ bool fieldn_supported(const fetode_field_t* f) {
   return true;
 }
 
+// fieldn_kernel's instantiations: the fixed-grid launch with the plan in global memory or staged in
+// LDS (ldsp), and the resident dopri5 driver, plain or taped (the plan in global memory)
+fused_fn fieldn_fn(bool ferro, bool dopri, bool tape, bool ldsp) {
+  if (!dopri && ldsp) return ferro ? fieldn_kernel<true, false, false, true> : fieldn_kernel<false, false, false, true>;
+  if (!dopri) return ferro ? fieldn_kernel<true> : fieldn_kernel<false>;
+  if (ferro) return tape ? fieldn_kernel<true, true, true> : fieldn_kernel<true, true, false>;
+  return tape ? fieldn_kernel<false, true, true> : fieldn_kernel<false, true, false>;
+}
+
 int launch_fused(const fetode_field_t* f, FusedArgs& a, void* stream) {
   const FusedEntry* e = find_fused(f);
   if (!e) {  // other widths: the generic single-launch kernel (inference and single evaluations)
     if (!fieldn_supported(f)) return set_err(FETODE_EUNSUPPORTED, "no fused kernel for this field shape");
-    layer_plan(f->kan[0], f->ferro ? &f->ferro[0] : nullptr, 0, &a.P0);
-    layer_plan(f->kan[1], f->ferro ? &f->ferro[1] : nullptr, a.P0.end, &a.P1);
+    field_plans(f, &a.P0, &a.P1);
     const int64_t pbytes = (int64_t)sizeof(float) * a.P1.end;
     const int tpw = 64 / fn_lanes_per_traj(a.P0.in, a.P0.out);
-    static const int lds_on = [] {  // FETODE_FIELDN_LDS=0: the plan read from global memory (A/B)
-      const char* e = getenv("FETODE_FIELDN_LDS");
-      return e ? atoi(e) : 1;
-    }();
+    // FETODE_FIELDN_LDS=0: the plan read from global memory (A/B)
+    static const int lds_on = (int)env_int("FETODE_FIELDN_LDS", 1);
     if (lds_on && pbytes <= kFnLdsMax) {
-      auto* kfn = f->ferro ? fieldn_kernel<true, false, false, true> : fieldn_kernel<false, false, false, true>;
+      const fused_fn kfn = fieldn_fn(f->ferro != nullptr, false, false, true);
       static bool attr[2] = {false, false};  // dynamic LDS beyond the 64 KB default
       if (!attr[f->ferro ? 1 : 0]) {
         HIP_CHECK_RET(hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFnLdsMax));
@@ -1918,18 +1920,14 @@ int launch_fused(const fetode_field_t* f, FusedArgs& a, void* stream) {
       hipLaunchKernelGGL(kfn, dim3(nblk(a.B, (int64_t)kFnWavesL * tpw)), dim3(64 * kFnWavesL), (size_t)pbytes,
                          (hipStream_t)stream, a);
     } else
-      hipLaunchKernelGGL(f->ferro ? fieldn_kernel<true> : fieldn_kernel<false>, dim3(nblk(a.B, (int64_t)kFnWaves * tpw)),
+      hipLaunchKernelGGL(fieldn_fn(f->ferro != nullptr, false, false, false), dim3(nblk(a.B, (int64_t)kFnWaves * tpw)),
                          dim3(64 * kFnWaves), 0, (hipStream_t)stream, a);
     LAUNCH_CHECK();
     return FETODE_OK;
   }
-  layer_plan(f->kan[0], f->ferro ? &f->ferro[0] : nullptr, 0, &a.P0);
-  layer_plan(f->kan[1], f->ferro ? &f->ferro[1] : nullptr, a.P0.end, &a.P1);
+  field_plans(f, &a.P0, &a.P1);
   a.img = a.P1.end;
-  static const float limit = [] {
-    const char* e = getenv("FETODE_FACTOR_LIMIT");
-    return e ? (float)atof(e) : kFactorLimit;
-  }();
+  static const float limit = (float)env_float("FETODE_FACTOR_LIMIT", kFactorLimit);
   a.factor_limit = limit;
   const bool rk4 = !a.single_eval && a.method == FETODE_RK4;
   if (rk4 && !a.tape && a.B > g_v8_lo && a.B <= g_v8_hi) {   // v8, two waves per trajectory
@@ -1949,12 +1947,7 @@ int launch_fused(const fetode_field_t* f, FusedArgs& a, void* stream) {
     // workgroups b and b + SIMD count share a SIMD: the arrangement that was measured)
     a.pair = a.pair_from = 0;
     if ((g_wave_skew > 0 || g_wave_prio) && rk4 && !a.tape && f->ferro) {
-      static const int n_simd = [] {
-        int dev = 0, n_cu = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-          return 0;
-        return 4 * n_cu;
-      }();
+      const int n_simd = 4 * device_cus();
       if (n_simd > 0 && nblk(a.B, 2) > n_simd && nblk(a.B, 2) <= 2 * n_simd) {
         a.pair = g_wave_skew | g_wave_prio << 8;
         a.pair_from = n_simd;
@@ -1979,8 +1972,7 @@ int fetode::fused_image_build(const fetode_field_t* f, float* plan, int64_t img,
   const FusedEntry* e = find_fused(f);
   if (!e) return FETODE_OK;
   LayerPlan P0, P1;
-  layer_plan(f->kan[0], f->ferro ? &f->ferro[0] : nullptr, 0, &P0);
-  layer_plan(f->kan[1], f->ferro ? &f->ferro[1] : nullptr, P0.end, &P1);
+  field_plans(f, &P0, &P1);
   if (img != P1.end) return set_err(FETODE_EINVAL, "plan image: offset %lld != end of the layer sections %lld",
                                     (long long)img, (long long)P1.end);
   hipLaunchKernelGGL(e->img_fn, dim3(nblk(e->img_floats, kImgBlock)), dim3(kImgBlock), 0, (hipStream_t)stream, P0, P1,
@@ -2097,78 +2089,21 @@ int64_t fetode_integrate_dopri5_multipass_max_batch(const fetode_field_t* f) {
   return e && e->dopri_mp ? kDpMultipassMaxBatch : 0;
 }
 
-// every workgroup must be resident at once (grid reductions): one-wave workgroups of two
-// trajectories, as many as the occupancy of the DOPRI instantiation admits (-1: query failed)
-// v6's dopri5 driver: one 192-thread workgroup per trajectory, every one resident
-static int64_t dopri5_small_resident_wgs(const FusedEntry* e, bool ferro) {
-  static int n_cu = 0, per_cu[2] = {0, 0};
-  const int fi = ferro ? 0 : 1;
-  if (!n_cu) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      return -1;
-  }
-  if (!per_cu[fi] && hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu[fi], e->small_dopri, 192, 0) != hipSuccess)
-    return -1;
-  return (int64_t)per_cu[fi] * n_cu;
-}
-
-static int64_t dopri5_resident_wgs(const FusedEntry* e, bool ferro) {
-  static int n_cu = 0, per_cu[2] = {0, 0};
-  const int fi = ferro ? 0 : 1;
-  if (!n_cu) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      return -1;
-  }
-  if (!per_cu[fi] && hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu[fi], e->dopri, 64, 0) != hipSuccess) return -1;
-  return (int64_t)per_cu[fi] * n_cu;
-}
-
-// the multi-pass driver's physical grid: its own occupancy (inference / taped)
-static int64_t dopri5_mp_resident_wgs(const FusedEntry* e, bool ferro, bool tape) {
-  static int n_cu = 0, per_cu[2][2] = {{0, 0}, {0, 0}};
-  const int fi = ferro ? 0 : 1, ti = tape ? 1 : 0;
-  if (!n_cu) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      return -1;
-  }
-  if (!per_cu[fi][ti] &&
-      hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu[fi][ti], tape ? e->dopri_mp_tape : e->dopri_mp, 64, 0) != hipSuccess)
-    return -1;
-  return (int64_t)per_cu[fi][ti] * n_cu;
-}
-
-// fieldn's dopri5 driver: one trajectory per one-wave workgroup, every one resident
-static const void* fieldn_dopri_fn(bool ferro, bool tape) {
-  return ferro ? (tape ? (const void*)fieldn_kernel<true, true, true> : (const void*)fieldn_kernel<true, true, false>)
-               : (tape ? (const void*)fieldn_kernel<false, true, true> : (const void*)fieldn_kernel<false, true, false>);
-}
-static int64_t dopri5_fieldn_resident_wgs(bool ferro, bool tape = false) {
-  static int n_cu = 0, per_cu[2][2] = {{0, 0}, {0, 0}};
-  const int fi = ferro ? 0 : 1, ti = tape ? 1 : 0;
-  if (!n_cu) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      return -1;
-  }
-  if (!per_cu[fi][ti] && hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu[fi][ti], fieldn_dopri_fn(ferro, tape), 64, 0) !=
-                             hipSuccess)
-    return -1;
-  return (int64_t)per_cu[fi][ti] * n_cu;
-}
-
+// Every workgroup of a dopri5 launch must be resident at once (grid reductions), so each kernel's grid
+// is bounded by its own resident_wgs (-1: query failed): v4 one-wave workgroups of two trajectories,
+// v6 one 192-thread workgroup per trajectory, the multi-pass driver's physical grid, and fieldn's
+// one-wave workgroups of one trajectory.
 int64_t fetode_integrate_dopri5_max_batch(const fetode_field_t* f, int32_t sharded) {
   if (validate_field(f) != FETODE_OK) return 0;
   const FusedEntry* e = find_fused(f);
   if (!e && fieldn_supported(f)) {  // the taped variant's grid bounds training solves too
-    const int64_t w0 = dopri5_fieldn_resident_wgs(f->ferro != nullptr), w1 = dopri5_fieldn_resident_wgs(f->ferro != nullptr, true);
+    const int64_t w0 = resident_wgs(fieldn_fn(f->ferro != nullptr, true, false, false), 64);
+    const int64_t w1 = resident_wgs(fieldn_fn(f->ferro != nullptr, true, true, false), 64);
     const int64_t w = (w0 < w1 ? w0 : w1) - (sharded ? 1 : 0);
     return w > 0 ? w : 0;
   }
   if (!e) return 0;
-  const int64_t w = dopri5_resident_wgs(e, f->ferro != nullptr) - (sharded ? 1 : 0);
+  const int64_t w = resident_wgs(e->dopri, 64) - (sharded ? 1 : 0);
   return w > 0 ? 2 * w : 0;
 }
 
@@ -2191,22 +2126,22 @@ static int dopri5_launch(const fetode_field_t* f, const void* plan, const float*
   const bool sharded = xr && xr->world > 1;
   // small batches (the reference's own X0 (1, 2); the strong-scaled shard): v6, one trajectory per
   // workgroup, when the whole grid is resident; else v4, two per one-wave workgroup
-  const int64_t res6 = (!fn && !sharded && B <= small_max()) ? dopri5_small_resident_wgs(e, f->ferro != nullptr) : -1;
+  const int64_t res6 = (!fn && !sharded && B <= small_max()) ? resident_wgs(e->small_dopri, 192) : -1;
   // multi-pass (fetode_dopri5_set_multipass): the v4 grid of this batch as the VIRTUAL grid of a
   // launch of at most `limit` / the co-resident capacity workgroups, when it does not fit one grid
   const bool mp_can = dp_multipass() && !fn && !sharded && B <= kDpMultipassMaxBatch;
   const int64_t mp_limit = mp_can ? dp_grid_limit() : 0;
   const bool mp_forced = mp_limit > 0 && nblk(B, 2) > mp_limit;
   const bool use6 = res6 >= B && !mp_forced;
-  const int64_t resident = fn ? dopri5_fieldn_resident_wgs(f->ferro != nullptr, tape_cap > 0)
-                              : use6 ? res6 : dopri5_resident_wgs(e, f->ferro != nullptr);
+  const int64_t resident = fn ? resident_wgs(fieldn_fn(f->ferro != nullptr, true, tape_cap > 0, false), 64)
+                              : use6 ? res6 : resident_wgs(e->dopri, 64);
   if (resident < 0) return set_err(FETODE_EHIP, "dopri5: occupancy query failed");
   const int per = fn ? 1 : 2;  // trajectories per workgroup (v6: one, never sharded)
   const int64_t grid = (use6 || fn) ? B : nblk(B, 2);
   int64_t lgrid = grid + (sharded ? 1 : 0);   // + the cross-rank exchange workgroup
   const bool mp = mp_can && (mp_forced || lgrid > resident);
   if (mp) {   // the physical grid: never more than the multi-pass kernel's own occupancy
-    const int64_t res_mp = dopri5_mp_resident_wgs(e, f->ferro != nullptr, tape_cap > 0);
+    const int64_t res_mp = resident_wgs(tape_cap > 0 ? e->dopri_mp_tape : e->dopri_mp, 64);
     if (res_mp <= 0) return set_err(FETODE_EHIP, "dopri5: occupancy query failed");
     lgrid = std::min(grid, res_mp);
     if (mp_limit > 0) lgrid = std::min(lgrid, mp_limit);
@@ -2289,18 +2224,17 @@ static int dopri5_launch(const fetode_field_t* f, const void* plan, const float*
   P.leaf_lo = (P.wg_off >> (P.leaf_shift + 3)) * 8;
   P.n_leaf_local = (int32_t)nleaves(grid, P.leaf_shift);
   P.n_leaf_global = (int32_t)nleaves(P.nblk_global, P.leaf_shift);
-  layer_plan(f->kan[0], f->ferro ? &f->ferro[0] : nullptr, 0, &a.P0);
-  layer_plan(f->kan[1], f->ferro ? &f->ferro[1] : nullptr, a.P0.end, &a.P1);
+  field_plans(f, &a.P0, &a.P1);
   a.img = a.P1.end;
   a.factor_limit = kFactorLimit;
   hipStream_t s = (hipStream_t)stream;
   HIP_CHECK_RET(hipMemsetAsync(workspace, 0, sizeof(unsigned) * kDpBarWords, s));
   void* args[] = {&a};
-  const void* kfn = fn ? fieldn_dopri_fn(f->ferro != nullptr, a.tape != nullptr)
-                   : mp ? (const void*)(a.tape ? e->dopri_mp_tape : e->dopri_mp)
-                   : use6 ? (const void*)(a.tape ? e->small_dopri_tape : e->small_dopri)
-                          : (const void*)(a.tape ? e->dopri_tape : e->dopri);
-  HIP_CHECK_RET(resident_launch(kfn, dim3((unsigned)lgrid), dim3(use6 ? 192 : 64), args, 0, s));
+  const fused_fn kfn = fn ? fieldn_fn(f->ferro != nullptr, true, a.tape != nullptr, false)
+                       : mp ? (a.tape ? e->dopri_mp_tape : e->dopri_mp)
+                       : use6 ? (a.tape ? e->small_dopri_tape : e->small_dopri)
+                              : (a.tape ? e->dopri_tape : e->dopri);
+  HIP_CHECK_RET(resident_launch((const void*)kfn, dim3((unsigned)lgrid), dim3(use6 ? 192 : 64), args, 0, s));
   return FETODE_OK;
 }
 

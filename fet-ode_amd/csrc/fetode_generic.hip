@@ -304,10 +304,8 @@ int fetode_kanlinear_forward(const fetode_kanlinear_t* kl, const float* x, int64
   if (kl->out_features >= 16 && kl->num_logistic <= kNBMax && kl->grid_size == 5 && kl->spline_order == 3) {
     // outputs per wave: the largest of 8/4/2/1 that still gives >= 1024 workgroups (4 per CU); fewer
     // outputs per wave recompute the features more often but fill the chip at small batches
-    static const int64_t min_blocks = [] {
-      const char* e = getenv("FETODE_WAVE_MIN_BLOCKS");  // tuning knob (default 1024, measured r01_s5)
-      return e ? (int64_t)atoll(e) : (int64_t)1024;
-    }();
+    // tuning knob (default 1024, measured r01_s5)
+    static const int64_t min_blocks = env_int("FETODE_WAVE_MIN_BLOCKS", 1024);
     const int64_t rb = (B + 63) / 64;
     int ob = 8;
     while (ob > 1 && rb * ((kl->out_features + 4 * ob - 1) / (4 * ob)) < min_blocks) ob >>= 1;

@@ -844,10 +844,7 @@ __global__ void wide_reduce_kernel(const float* __restrict__ part, int S, int64_
 
 // the LDS (workgroup-per-image) Kuramoto kernels for every shape: FETODE_KURA_LDS=1 (A/B and the
 // cross-check test), or fetode_kuramoto_set_lds(1)
-int g_kura_lds = [] {
-  const char* e = getenv("FETODE_KURA_LDS");
-  return e ? atoi(e) : 0;
-}();
+int g_kura_lds = (int)env_int("FETODE_KURA_LDS", 0);
 bool kura_lds_forced() { return g_kura_lds != 0; }
 
 int wide_supported(const fetode_kanlinear_t* kl) {
@@ -975,10 +972,8 @@ int fetode_kanlinear_wide_forward(const fetode_kanlinear_t* kl, const float* wpa
   const int64_t tiles = (B + kWideRows - 1) / kWideRows;
   if (tiles > 0x7fffffff) return set_err(FETODE_EINVAL, "kanlinear wide: batch too large");
   hipStream_t s = (hipStream_t)stream;
-  static const int v1 = [] {  // FETODE_WIDE_V=1: wide_fwd_kernel, one tile per wave (A/B, bitwise the same)
-    const char* e = getenv("FETODE_WIDE_V");
-    return e ? atoi(e) : 0;
-  }();
+  // FETODE_WIDE_V=1: wide_fwd_kernel, one tile per wave (A/B, bitwise the same)
+  static const int v1 = (int)env_int("FETODE_WIDE_V", 0);
   if (v1 == 1) {
     hipLaunchKernelGGL(wide_fwd_kernel, dim3((unsigned)tiles, (unsigned)S), dim3(kWideThreads), 0, s, *kl, wpack, x, B,
                        nch, (float*)workspace);

@@ -625,10 +625,7 @@ wide_fn pick_ch(int K, bool kan, bool ferro) {
 // inputs per staged chunk: 8 (fewer barriers) or 4 (less LDS, more resident workgroups);
 // FETODE_WIDE_CH picks (tuning knob, default 8)
 wide_fn pick(int K, bool kan, bool ferro) {
-  static const int ch = [] {
-    const char* e = getenv("FETODE_WIDE_CH");
-    return e && atoi(e) == 4 ? 4 : 8;
-  }();
+  static const int ch = (int)env_int("FETODE_WIDE_CH", 8) == 4 ? 4 : 8;
   return ch == 4 ? pick_ch<4>(K, kan, ferro) : pick_ch<8>(K, kan, ferro);
 }
 
@@ -654,12 +651,8 @@ wide_fn pick(int K, bool kan, bool ferro) {
 // output groups per wave: 2 (default; 4 holds ~220 VGPRs, two waves per SIMD); FETODE_FERRO_BWD_OGW
 // = 1 | 2 | 4 picks (tuning knob)
 int ferro_bwd_ogw() {
-  static const int v = [] {
-    const char* e = getenv("FETODE_FERRO_BWD_OGW");
-    const int x = e ? atoi(e) : 2;
-    return x == 1 || x == 4 ? x : 2;
-  }();
-  return v;
+  static const int x = (int)env_int("FETODE_FERRO_BWD_OGW", 2);
+  return x == 1 || x == 4 ? x : 2;
 }
 
 struct WideFerroBwdArgs {
@@ -852,22 +845,12 @@ __global__ __launch_bounds__(256) void wide_ferro_bwd_kernel(WideFerroBwdArgs a)
 
 // resident waves of wide_ferro_bwd_kernel on the device (CUs x 4 waves x blocks per CU), 0 unknown
 int ferro_bwd_slots(int K) {
-  static int slots[2] = {-1, -1};
-  int& v = slots[K == 12 ? 1 : 0];
-  if (v < 0) {
-    v = 0;
-    int dev = 0, n_cu = 0, per = 0;
-    const int ogw = ferro_bwd_ogw();
-    const void* fn = K == 12 ? (ogw == 1 ? (const void*)wide_ferro_bwd_kernel<12, 1>
-                                : ogw == 4 ? (const void*)wide_ferro_bwd_kernel<12, 4> : (const void*)wide_ferro_bwd_kernel<12, 2>)
-                             : (ogw == 1 ? (const void*)wide_ferro_bwd_kernel<10, 1>
-                                : ogw == 4 ? (const void*)wide_ferro_bwd_kernel<10, 4> : (const void*)wide_ferro_bwd_kernel<10, 2>);
-    if (hipGetDevice(&dev) == hipSuccess &&
-        hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess &&
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, fn, 256, 0) == hipSuccess)
-      v = n_cu * per * 4;
-  }
-  return v;
+  const int ogw = ferro_bwd_ogw();
+  const void* fn = K == 12 ? (ogw == 1 ? (const void*)wide_ferro_bwd_kernel<12, 1>
+                              : ogw == 4 ? (const void*)wide_ferro_bwd_kernel<12, 4> : (const void*)wide_ferro_bwd_kernel<12, 2>)
+                           : (ogw == 1 ? (const void*)wide_ferro_bwd_kernel<10, 1>
+                              : ogw == 4 ? (const void*)wide_ferro_bwd_kernel<10, 4> : (const void*)wide_ferro_bwd_kernel<10, 2>);
+  return (int)std::max<int64_t>(resident_wgs(fn, 256), 0) * 4;
 }
 
 FerroBwdPlan ferro_bwd_plan(int in, int out, int K, int64_t B) {
@@ -883,10 +866,7 @@ FerroBwdPlan ferro_bwd_plan(int in, int out, int K, int64_t B) {
   // fixes it (tuning knob).
   const int64_t base = (int64_t)p.n_ogb * in;
   const int64_t rmax = std::max<int64_t>(1, std::min<int64_t>(64, (B + 63) / 64));
-  static const int rs_env = [] {
-    const char* e = getenv("FETODE_FERRO_BWD_RS");
-    return e ? atoi(e) : 0;
-  }();
+  static const int rs_env = (int)env_int("FETODE_FERRO_BWD_RS", 0);
   int64_t rs = 1;
   const int slots = ferro_bwd_slots(K);
   if (rs_env > 0) {
@@ -2086,20 +2066,12 @@ int wide_dopri5_launch(const fetode_kanlinear_t* kan0, const fetode_ferro_t* fer
   const int K = fer0->num_basis;
   const void* fn = K == 12 ? (const void*)wide_dopri5_kernel<12> : (const void*)wide_dopri5_kernel<10>;
   // persistent grid: every workgroup resident at once (the phases meet at grid barriers)
-  static int per_cu[2] = {0, 0}, n_cu = 0;
-  const int fi = K == 12 ? 1 : 0;
-  if (!n_cu) {
-    int dev = 0;
-    HIP_CHECK_RET(hipGetDevice(&dev));
-    HIP_CHECK_RET(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
-  }
-  if (!per_cu[fi]) HIP_CHECK_RET(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu[fi], fn, kThreads, 0));
+  const int64_t resident = resident_wgs(fn, kThreads);
+  if (resident < 0) return set_err(FETODE_EHIP, "wide dopri5: occupancy query failed");
   const int64_t want = std::max<int64_t>((int64_t)sh.nT0 * sh.S0, (int64_t)sh.nT1 * sh.S1);
-  int64_t grid = std::min<int64_t>({want, (int64_t)per_cu[fi] * n_cu, (int64_t)kWideDopriMaxGrid});
-  static const int64_t grid_cap = [] {  // diagnostics: cap the persistent grid (FETODE_WIDE_DOPRI_GRID)
-    const char* e = getenv("FETODE_WIDE_DOPRI_GRID");
-    return e ? (int64_t)atoll(e) : (int64_t)0;
-  }();
+  int64_t grid = std::min<int64_t>({want, resident, (int64_t)kWideDopriMaxGrid});
+  // diagnostics: cap the persistent grid (FETODE_WIDE_DOPRI_GRID)
+  static const int64_t grid_cap = env_int("FETODE_WIDE_DOPRI_GRID", 0);
   if (grid_cap > 0) grid = std::min(grid, grid_cap);
   if (grid < 1) return set_err(FETODE_EHIP, "wide dopri5: no resident workgroup");
   WideDopriArgs a{};

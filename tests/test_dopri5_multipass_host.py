@@ -94,6 +94,25 @@ def test_max_batch_by_shape(lib_off):
     assert mb(ctypes.byref(_field(L))) == cap
 
 
+def test_capacity_exports_answer_without_a_device(lib_off):
+    """The capacity exports size their answer by the device's resident workgroups; with no device the
+    query fails and they answer 0 (or a negative value, ECG) instead of crashing.  With a device every
+    one of them is positive."""
+    import torch
+    L, lib = lib_off
+    fields = (_field(L), _field(L, ferro=False), _field(L, H=12), _field(L, H=12, ferro=False))
+    fwd = [lib.fetode_integrate_dopri5_max_batch(ctypes.byref(f), s) for f in fields for s in (0, 1)]
+    bwd = [lib.fetode_integrate_dopri5_backward_max_batch(ctypes.byref(f)) for f in fields]
+    layer = L.HLogisticDesc(8, 10, FAKE, FAKE, FAKE, FAKE, 5.0, 0.5)
+    ecg = lib.fetode_ecg_dopri5_backward_max_batch(ctypes.byref(layer))
+    if torch.cuda.is_available():
+        assert min(fwd) > 0 and min(bwd) > 0 and ecg > 0, (fwd, bwd, ecg)
+    else:
+        assert fwd == [0] * 8, fwd
+        assert bwd == [0] * 4, bwd
+        assert ecg <= 0, ecg
+
+
 def test_workspace_includes_parking_only_when_on(lib_off):
     L, lib = lib_off
     ws = lib.fetode_integrate_dopri5_workspace
