@@ -366,6 +366,15 @@ __device__ __forceinline__ f2 v4_pair(f2 ew, f2 xp, f2 ep, f2 k2, f2 kE, f2 cp, 
   return pfma(cp, th, acc);
 }
 
+// the single element from its gate sigmoid s on (the caller that forms s itself: the body's packed
+// hidden-phase chains)
+__device__ __forceinline__ float v4_single_from(float s, f2 ew, f2 xp, float k2, float kE, float cp, float acc) {
+  const float m = ffma(ew.y, s, 1.0f);
+  const float z = ffma(kE, m, k2 * xp.x);
+  const float th = ffma(rcp(ex2(z) + 1.0f), -2.0f, 1.0f);
+  return ffma(cp, th, acc);
+}
+
 // one Ferro element (the single leftover of a layer's pair split): acc + cps * tanh(...)
 template <bool FACT>
 __device__ __forceinline__ float v4_single(f2 ew, f2 xp, float ep, float k2, float kE, float cp, float acc,
@@ -376,10 +385,7 @@ __device__ __forceinline__ float v4_single(f2 ew, f2 xp, float ep, float k2, flo
   } else {
     s = rcp(ex2(ffma(gsl2e, xp.x, ep)) + 1.0f);
   }
-  const float m = ffma(ew.y, s, 1.0f);
-  const float z = ffma(kE, m, k2 * xp.x);
-  const float th = ffma(rcp(ex2(z) + 1.0f), -2.0f, 1.0f);
-  return ffma(cp, th, acc);
+  return v4_single_from(s, ew, xp, k2, kE, cp, acc);
 }
 
 // the edge sum of one lane: NPL Ferro pairs (+ NSL single elements), FPL feature weights, and

@@ -34,6 +34,14 @@
   // batch (EBF, 8 more registers) in the rk4 kernels only: the generic and taped kernels would drop
   // from 3 to 2 waves per SIMD, the taped dopri5 and multi-pass kernels would spill
   constexpr bool EB0 = FERRO, EBF0 = EB0 && HOT;
+  // the hidden phase's independent sigmoid-of-affine chains issued two to a packed instruction (PKS,
+  // DESIGN.md §3 round 11): the two rk4 inference kernels only, the instantiations the listing and
+  // the resource table were checked for; every other one keeps the scalar chains, line for line
+#ifndef FETODE_EXP_NO_PK_CHAINS
+  constexpr bool PKS = FERRO && HOT && !TAPE;
+#else
+  constexpr bool PKS = false;
+#endif
   // bit r: round r reads the row round r - 1 read, on every lane (gi0 below): it is read once
   constexpr unsigned SAME0 = [] {
     unsigned m = 0;
@@ -235,6 +243,15 @@
     fml1[r] = silu ? 1.f : 0.f;
     fwt1[r] = f2{LI(s + 2), LI(s + 3)};
   }
+  // PKS: the affine coefficients of feature rounds (2 p, 2 p + 1) as pairs, the gate's and the factored
+  // exponential's slopes (gs, -gs) as one, and the single's gate constant beside the gate's 1
+  f2 fna2[RF1 / 2 > 0 ? RF1 / 2 : 1], fab2[RF1 / 2 > 0 ? RF1 / 2 : 1];
+#pragma unroll
+  for (int p = 0; p < RF1 / 2; ++p) {
+    fna2[p] = f2{fna1[2 * p], fna1[2 * p + 1]};
+    fab2[p] = f2{fab1[2 * p], fab1[2 * p + 1]};
+  }
+  const f2 gsn1 = f2{a.P1.gsl2e, -a.P1.gsl2e}, es1p = f2{es1, 1.0f};
   // ---- layer-0 feature stream: input d = row, job c1 ----
   float xna, xab, xmul, xadd;
   float* xdst;
@@ -384,16 +401,64 @@
       const int mfix = (unsigned)mm < (unsigned)NI ? mm : NI;
       // spline operands by interval (the zero row NI holds (0, 0): u = 0 for finite h, NaN
       // otherwise, as the reference's bases); their LDS latency hides under the pairs
-      const float4 cf = *reinterpret_cast<const float4*>(&sp1_e[mfix * 4]);
+      // PKT (two per wave, where the single exists): the cubic's last two Horner steps share two packed
+      // FMAs with the single's last two links, (t u + y, r (-2) + 1) and (. u + x, th cp + 0), the
+      // scalar forms' operations (the compiler paired them already, with three moves that put y, x and
+      // a second u beside their constants).  y and x are read on their own, each into the low half of
+      // a pair whose high half holds the constant, z and w as one pair: two more LDS reads, two
+      // fewer VALU moves.
+#ifndef FETODE_EXP_NO_PK_TAIL
+      constexpr bool PKT = PKS && NSL1 > 0;
+#else
+      constexpr bool PKT = false;
+#endif
+      float4 cf = make_float4(0.f, 0.f, 0.f, 0.f);
+      float cx = 0.f, cy = 0.f, rs1 = 0.f;   // rs1: the single's last reciprocal
+      f2 czw = splat(0.f);
+      if constexpr (PKT) {
+        cx = lds_now(&sp1_e[mfix * 4]);
+        cy = lds_now(&sp1_e[mfix * 4 + 1]);
+        czw = lds_now(reinterpret_cast<const f2*>(&sp1_e[mfix * 4 + 2]));
+      } else {
+        cf = *reinterpret_cast<const float4*>(&sp1_e[mfix * 4]);
+      }
       const f2 kw = kr1_o[mfix];
       float sgl = 0.0f;
       if constexpr (FERRO) {
         // every lane of the group forms the gate and exp(gs h) of its input itself (three
         // transcendentals: cheaper than broadcasting them across a group of 3 lanes)
         const float pv = re1 ? h : prev1;
-        const float eg = ex2(ffma(-a.P1.gsl2e, h - pv, 0.0f));
-        const float w = ffma(rcp(1.0f + eg), -a.P1.wc, a.P1.wc);   // wc (1 - up)
-        const float e = F_ ? ex2(ffma(a.P1.gsl2e, h, 0.0f)) : 0.0f;
+        float w, e = 0.0f, s1 = 0.0f;   // s1: the single's gate sigmoid (PKS)
+        if constexpr (PKS) {
+          // The gate's chain and the single's first link share their instructions, component for
+          // component the scalar form's IEEE operations: (gs h + 0, -gs (h - pv) + 0) is one packed
+          // FMA, and the gate's 1 + eg is fma(eg, 1, 1), one rounding of the same sum, beside the
+          // single's fma(e, ep, 1) (factored) or its exp2 + 1 (unfactored: a packed add).
+          float eg;
+          if constexpr (F_) {
+            const f2 ge = ex2x2(pfma(gsn1, f2{h, h - pv}, splat(0.0f)));
+            e = ge.x;
+            eg = ge.y;
+            if constexpr (NSL1 > 0) {
+              const f2 r = rcpx2(pfma(ge, es1p, splat(1.0f)));
+              s1 = r.x;
+              w = ffma(r.y, -a.P1.wc, a.P1.wc);
+            }
+          } else {
+            eg = ex2(ffma(-a.P1.gsl2e, h - pv, 0.0f));
+            if constexpr (NSL1 > 0) {
+              const float d1 = ex2(ffma(a.P1.gsl2e, h, es1));
+              const f2 r = rcpx2(f2{eg, d1} + splat(1.0f));
+              w = ffma(r.x, -a.P1.wc, a.P1.wc);
+              s1 = r.y;
+            }
+          }
+          if constexpr (NSL1 == 0) w = ffma(rcp(1.0f + eg), -a.P1.wc, a.P1.wc);
+        } else {
+          const float eg = ex2(ffma(-a.P1.gsl2e, h - pv, 0.0f));
+          w = ffma(rcp(1.0f + eg), -a.P1.wc, a.P1.wc);   // wc (1 - up)
+          e = F_ ? ex2(ffma(a.P1.gsl2e, h, 0.0f)) : 0.0f;
+        }
         prev1 = h;   // ferro_class.py:409
         re1 = false;
         const f2 ew = f2{e, w}, xp = f2{h, 0.0f};
@@ -403,7 +468,14 @@
 #ifdef FETODE_EXP_L1_DROP
         PRIO_LO();
 #endif
-        if constexpr (NSL1 > 0) sgl = v4_single<F_>(ew, xp, es1, k2s1, kEs1, cps1, 0.0f, a.P1.gsl2e);
+        if constexpr (NSL1 > 0) {
+          if constexpr (PKT) {
+            const float m = ffma(ew.y, s1, 1.0f);
+            const float z = ffma(kEs1, m, k2s1 * xp.x);
+            rs1 = rcp(ex2(z) + 1.0f);
+          } else if constexpr (PKS) sgl = v4_single_from(s1, ew, xp, k2s1, kEs1, cps1, 0.0f);
+          else sgl = v4_single<F_>(ew, xp, es1, k2s1, kEs1, cps1, 0.0f, a.P1.gsl2e);
+        }
 #pragma unroll
         for (int r = 0; r < NPL1; ++r) acc01 = v4_pair<F_>(ew, xp, ep1[r], k21[r], kE1[r], cp1[r], acc01, a.P1.gsl2e);
 #ifdef FETODE_EXP_L1_DROP
@@ -411,16 +483,33 @@
 #endif
       }
       // the group's features (SiLU + NB logistic), each weighted for both outputs
+      // (PKS: rounds 2 p and 2 p + 1 share the affine FMA and the + 1, each component the scalar round's
+      // operation; the accumulation keeps the rounds' order)
 #pragma unroll
-      for (int r = 0; r < RF1; ++r) {
+      for (int p = 0; p < (PKS ? RF1 / 2 : 0); ++p) {
+        const f2 sg = rcpx2(splat(1.0f) + ex2x2(pfma(fna2[p], splat(h), fab2[p])));
+        const float v0 = fml1[2 * p] != 0.0f ? h * sg.x : sg.x;
+        const float v1 = fml1[2 * p + 1] != 0.0f ? h * sg.y : sg.y;
+        acc01 = pfma(fwt1[2 * p], splat(v0), acc01);
+        acc01 = pfma(fwt1[2 * p + 1], splat(v1), acc01);
+      }
+#pragma unroll
+      for (int r = PKS ? RF1 / 2 * 2 : 0; r < RF1; ++r) {
         const float e = ex2(ffma(fna1[r], h, fab1[r]));
         const float sg = rcp(1.0f + e);
         const float val = fml1[r] != 0.0f ? h * sg : sg;   // SiLU h sigma(h) / logistic sigma
         acc01 = pfma(fwt1[r], splat(val), acc01);
       }
       const float u = (h - kw.x) * kw.y;
-      const float sv = ffma(ffma(ffma(cf.w, u, cf.z), u, cf.y), u, cf.x);
-      acc01 = pfma(dsel1, splat(sgl + sv), acc01);   // lane d < 2: single + spline onto output d
+      if constexpr (PKT) {
+        const float t = ffma(czw.y, u, czw.x);
+        const f2 p1 = pfma(f2{t, rs1}, f2{u, -2.0f}, f2{cy, 1.0f});
+        const f2 p2 = pfma(p1, f2{u, cps1}, f2{cx, 0.0f});
+        acc01 = pfma(dsel1, splat(p2.y + p2.x), acc01);
+      } else {
+        const float sv = ffma(ffma(ffma(cf.w, u, cf.z), u, cf.y), u, cf.x);
+        acc01 = pfma(dsel1, splat(sgl + sv), acc01);   // lane d < 2: single + spline onto output d
+      }
 #ifndef FETODE_EXPERIMENT_NO_TAPE_STORE
       // the evaluation's tape row in ONE non-temporal store: h_o from the group's first lane, x_row
       // from the row's idle lane 15 (two plain stores cost the B = 4096 taped solve 23 us over none,
@@ -487,6 +576,26 @@
     // rk4 (torchdiffeq rk_common.rk4_alt_step_func op order); the step's first two output
     // slots are read before its stages and consumed after them, with predicated stores
     int sb = 0, jb = 1, jj = 1;
+    // the solution element of output row jj this lane stores, carried and advanced by the row stride
+    // with jj (out_write's address, not rebuilt from jj per store)
+#ifndef FETODE_EXP_NO_OUT_PTR
+    constexpr bool OPTR = true;
+#else
+    constexpr bool OPTR = false;
+#endif
+    float* outp = a.solution + (a.B + (valid ? b : 0)) * D + row;
+    const int64_t out_stride = a.B * D;
+    auto out_next = [&](float v) __attribute__((always_inline)) {
+      if constexpr (OPTR) {
+#ifndef FETODE_EXPERIMENT_NO_OUT
+        if (valid && own && c1 == 0) *outp = v;
+#endif
+        outp += out_stride;
+      } else {
+        out_write(jj, v);
+      }
+      ++jj;
+    };
     auto run = [&](auto fact_tag, auto prio_tag, int s_from, int s_to) __attribute__((always_inline)) {
       const float third = 1.0f / 3.0f;
       for (int s = s_from; s < s_to; ++s) {
@@ -515,8 +624,7 @@
           asm volatile("" : "+v"(m0), "+v"(sl0));
           const float oip = y + sl0 * (y1 - y);
           const float o1 = m0 == 1 ? y1 : oip;
-          out_write(jj, m0 == 0 ? y : o1);
-          ++jj;
+          out_next(m0 == 0 ? y : o1);
           if (os1 == s) {  // several outputs inside one step (step_size grids)
             while (jj < a.T) {
               if (jj - jb == SCH) {
@@ -525,8 +633,7 @@
               }
               if (s_ostep[jj - jb] != s) break;
               const int mode = s_omode[jj - jb];
-              out_write(jj, mode == 0 ? y : (mode == 1 ? y1 : y + s_oslope[jj - jb] * (y1 - y)));
-              ++jj;
+              out_next(mode == 0 ? y : (mode == 1 ? y1 : y + s_oslope[jj - jb] * (y1 - y)));
             }
           }
         }
