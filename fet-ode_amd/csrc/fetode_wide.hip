@@ -1275,6 +1275,14 @@ struct WideDopriArgs {
   unsigned xr_epoch;
   double* const* xr_peers;     // (dev) every rank's inbox as mapped here (peers[rank] = own)
   double* xr_inbox;
+  // the training tape (wide_dopri5_tape_kernel alone reads these): three planes, one row block per
+  // evaluation e < tape_cap — x_e (B, D) the layer-0 input, h_e (B, H) the hidden (the slabs'
+  // fixed-order sum), k_e (B, D) the output
+  float* tpx;
+  float* tph;
+  float* tpk;
+  int64_t tape_cap;
+  double* init_rec;  // {d0, d1, d2, h0, h1}
 };
 
 __device__ __forceinline__ void st_wt(float* p, float v) {  // write-through (sc1) store
@@ -1477,320 +1485,23 @@ struct WdCtl {
 };
 enum { kNextNone = 0, kNextProbe = 1, kNextAttempt = 2 };
 
-template <int K>
-__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4))) void wide_dopri5_kernel(WideDopriArgs a) {
-  __shared__ WdCtl ctl;
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int G = (int)gridDim.x;
-  const int64_t B = a.B, BD = B * a.D, BH = B * a.H;
-  const int D = a.D, H = a.H;
-  const double n_el = a.n_el;
-  // element ownership: the layer-1 tile epilogue's storing threads (waves 0-3: row 16 (w % 4) +
-  // 4 (lane / 16) + v, dim lane % 16), layer-1 tile t < nT1 on workgroup t % G
-  const bool owner = w < 4;
-  const int rt = w & 3, kq = lane >> 4, kr = lane & 15;
-  auto for_owned = [&](auto&& f) {
-    if (!owner) return;
-    for (int t = blockIdx.x; t < a.nT1; t += G) {
-      const int64_t b0 = (int64_t)(t / a.nOT1) * kRows;
-      const int d = (t % a.nOT1) * kOuts + kr;
-#pragma unroll
-      for (int v = 0; v < 4; ++v) {
-        const int64_t b = b0 + 16 * rt + 4 * kq + v;
-        if (b < B) f(b * D + d);
-      }
-    }
-  };
-  float* const es = a.es;
-  unsigned nround = 0;  // norm rounds (wide_norm)
-
-  for_owned([&](int64_t i) {
-    const float y = a.y0[i];
-    es[kEY * BD + i] = y;
-    a.sol[i] = y;
-  });
-  if (tid == 0) {
-    ctl.dt = a.step.first_step;
-    ctl.t0 = ctl.t1 = 0.0;
-    ctl.t0s = ctl.t1s = a.t[0];
-    ctl.h0 = ctl.d1 = ctl.dt32 = 0.f;
-    ctl.nev = ctl.nfev = ctl.n_att = ctl.n_steps = ctl.stg = 0;
-    ctl.iout = 1;
-    ctl.kind = kCmbF0;
-    ctl.status = -1;
-  }
-  __syncthreads();
-  int status = -1;
-#pragma unroll 1
-  for (;;) {
-    // ---- one field evaluation: L0 phase | barrier | L1 phase | barrier ----
-    const int e = ctl.nev, p = e & 1;
-    if (e > 0 && wide_barrier(a.bar)) {  // the stage input came from other workgroups
-      status = 4;
-      break;
-    }
-    bool ab = false;
-#pragma unroll 1
-    for (int l = 0; l < 2 && !ab; ++l) {
-      WideArgs L = l ? a.l1 : a.l0;
-      const int nT = l ? a.nT1 : a.nT0, nOT = l ? a.nOT1 : a.nOT0, S = l ? a.S1 : a.S0;
-      if (l == 0) {
-        L.x = e == 0 ? a.y0 : a.xin + p * BD;
-        L.nxs = L.nps = 1;
-        L.reinit = e == 0 ? a.reinit0 : 0;
-        L.prev = e == 0 ? a.prev0 : (e == 1 ? a.y0 : a.xin + (p ^ 1) * BD);
-      } else {
-        L.x = a.hs + (int64_t)p * a.S0 * BH;
-        L.nxs = a.S0;
-        L.xss = BH;
-        L.reinit = e == 0 ? a.reinit1 : 0;
-        L.prev = e == 0 ? a.prev1 : a.hs + (int64_t)(p ^ 1) * a.S0 * BH;
-        L.nps = e == 0 ? 1 : a.S0;
-        L.pss = BH;
-      }
-      L.nslice = S;
-      const int ow = l ? D : H;
-      float* const ob = l ? a.ks : a.hs + (int64_t)p * a.S0 * BH;  // k slabs | this parity's hidden slabs
-      const int64_t sl = l ? BD : BH;
-      for (int t = blockIdx.x; t < nT * S; t += G) {
-        const int bz = t / nT, r = t % nT;
-        float* const o = ob + bz * sl;
-        wide_tile<K, true, true, kChMax, true>(L, r / nOT, r % nOT, bz,
-                                               [&](int64_t b, int c, float v) { st_wt(&o[b * ow + c], v); });
-      }
-      ab = wide_barrier(a.bar);
-    }
-    if (ab) {
-      status = 4;
-      break;
-    }
-    // ---- the per-element combine of k (the host loop's fetode_lincomb / scaled_rms order) ----
-    {
-      const int kind = ctl.kind, stg = ctl.stg, pn = (e + 1) & 1;
-      const float dt32 = ctl.dt32;
-      float c[8];
-#pragma unroll
-      for (int q = 0; q < 8; ++q) c[q] = ctl.cc[q];
-      const int S1 = a.S1;
-      // norm terms: per layer-1 tile (wide_tile_partial) when this evaluation ends in a reduction
-      const bool red = (kind == kCmbF0 && !(a.step.first_step > 0.0)) || kind == kCmbF1 || (kind == kCmbStage && stg == 5);
-      double acc0 = 0.0, acc1 = 0.0;
-      auto elem = [&](int64_t i) {
-        float k = a.ks[i];
-        for (int s = 1; s < S1; ++s) k = k + a.ks[s * BD + i];  // slab 0 + slab 1 + ..: the launch path's order
-        const float y = es[kEY * BD + i];
-        if (kind == kCmbF0) {  // f0 = f(t0, y0); _select_initial_step's d0 / d1 terms
-          es[kEF0 * BD + i] = k;
-          const float scale = a.atol + a.rtol * fabsf(y);
-          const float q0 = y / scale, q1 = k / scale;
-          acc0 += (double)q0 * q0;
-          acc1 += (double)q1 * q1;
-        } else if (kind == kCmbF1) {  // d2 term: (f1 - f0) / scale
-          const float scale = a.atol + a.rtol * fabsf(y);
-          const float q2 = (k - es[kEF0 * BD + i]) / scale;
-          acc0 += (double)q2 * q2;
-        } else {  // Dormand-Prince stage stg (k = k_{stg + 1}): the running sums take k's column
-          float a0 = 0.f;
-#pragma unroll
-          for (int q = 0; q < 5; ++q) {
-            const float v = es[(kEA + q + 1) * BD + i] + k * (c[q] * dt32);
-            es[(kEA + q) * BD + i] = v;
-            if (q == 0) a0 = v;
-          }
-          const float err = es[kEErr * BD + i] + k * (c[6] * dt32);
-          es[kEErr * BD + i] = err;
-          es[kEMid * BD + i] = es[kEMid * BD + i] + k * (c[7] * dt32);
-          if (stg < 5) {
-            const float yi = y + a0;
-            st_wt(a.xin + pn * BD + i, yi);
-            es[kEY1 * BD + i] = yi;
-          } else {  // FSAL: k is f(t1, y1); the error ratio's term and torchdiffeq's finiteness assert
-            es[kEKl * BD + i] = k;
-            const float y1 = es[kEY1 * BD + i];
-            const float tol = a.atol + a.rtol * fmaxf(fabsf(y), fabsf(y1));
-            const float qe = err / tol;
-            acc0 += (double)qe * qe;
-            acc1 += __builtin_isfinite(y) ? 0.0 : 1.0;
-          }
-        }
-      };
-      for (int t = blockIdx.x; t < a.nT1; t += G) {
-        if (owner) {
-          const int64_t b0 = (int64_t)(t / a.nOT1) * kRows;
-          const int d = (t % a.nOT1) * kOuts + kr;
-#pragma unroll
-          for (int v = 0; v < 4; ++v) {
-            const int64_t b = b0 + 16 * rt + 4 * kq + v;
-            if (b < B) elem(b * D + d);
-          }
-        }
-        if (red) {
-          wide_tile_partial(a.slot, t, acc0, acc1);
-          acc0 = acc1 = 0.0;
-        }
-      }
-    }
-    // ---- the decision (thread 0) ----
-    const int kind = ctl.kind, stg = ctl.stg;
-    const bool reduce = !(kind == kCmbF0 && a.step.first_step > 0.0) && !(kind == kCmbStage && stg < 5);
-    double s0 = 0.0, s1 = 0.0;
-    if (reduce && wide_norm(a, nround, s0, s1)) {
-      status = 4;
-      break;
-    }
-    __syncthreads();  // every wave has read this evaluation's control words before thread 0 rewrites them
-    if (tid == 0) {
-      ctl.nev = e + 1;
-      ++ctl.nfev;
-      ctl.fit = 0;
-      ctl.next = kNextNone;
-      ctl.io_lo = ctl.io_hi = ctl.iout;
-      bool sched = false;  // outputs due, then the next attempt
-      if (kind == kCmbStage && stg < 5) {
-        ctl.stg = stg + 1;
-        ctl.next = kNextNone;  // the combine already wrote the next stage input
-      } else if (kind == kCmbF0 && !(a.step.first_step > 0.0)) {  // the initial step: h0, then the probe
-        float d0, d1;
-        ctl.h0 = dopri_h0(s0, s1, n_el, d0, d1);
-        ctl.d1 = d1;
-        ctl.kind = kCmbF1;
-        ctl.next = kNextProbe;
-      } else if (kind == kCmbF1) {
-        float d2, h1;
-        ctl.dt = dopri_dt0(s0, n_el, ctl.h0, ctl.d1, d2, h1);
-        sched = true;
-      } else if (kind == kCmbF0) {  // first_step given
-        sched = true;
-      } else {  // the attempt's error ratio, accept / reject, rk_common._optimal_step_size
-        if (s1 != 0.0) {
-          ctl.status = 1;
-        } else {
-          const float ratio = dopri_ratio(s0, n_el);
-          const bool accept = dopri_accept(ratio);
-          if (blockIdx.x == 0) dopri_log_attempt(a.att, ctl.n_att, a.max_att, ctl.t0, ctl.dt, ratio, accept);
-          ++ctl.n_att;
-          if (accept) {
-            ctl.fit = 1;
-            ctl.fit_dt32 = ctl.dt32;  // the accepted attempt's step (dt32 is about to take the next one)
-            ctl.t0s = ctl.t0;
-            ctl.t1s = ctl.t1;
-          } else {
-            ctl.t0s = ctl.t0;
-          }
-          ctl.dt = dopri_next_dt(ctl.dt, ratio, a.step);
-          ++ctl.n_steps;
-          sched = true;
-        }
-      }
-      if (sched) {
-        // outputs due (interp._interp_evaluate of the last accepted step), then the next attempt
-        int io = ctl.iout;
-        while (io < a.T && !(a.t[io] > ctl.t1s)) {
-          ++io;
-          ctl.n_steps = 0;
-        }
-        ctl.io_hi = io;
-        ctl.iout = io;
-        if (io >= a.T) {
-          ctl.status = 0;
-        } else if (ctl.n_steps >= a.max_steps) {
-          ctl.status = 3;
-        } else {
-          const double t0 = ctl.t1s, dt = ctl.dt;
-          if (dopri_underflow(t0, dt)) {
-            ctl.status = 2;
-          } else {
-            ctl.t0 = t0;
-            ctl.t1 = t0 + dt;
-            ctl.dt32 = (float)dt;
-            ctl.kind = kCmbStage;
-            ctl.stg = 0;
-            ctl.next = kNextAttempt;
-          }
-        }
-      }
-      // the tableau column of the next stage evaluation's k (static indices: kernel-argument reads)
-#pragma unroll
-      for (int j = 1; j < 7; ++j)
-        if (j == ctl.stg + 1) {
-#pragma unroll
-          for (int q = 0; q < 8; ++q) ctl.cc[q] = a.stc[j][q];
-        }
-    }
-    __syncthreads();
-    // ---- the decision's element passes (owner threads only: no hand-off) ----
-    if (ctl.fit) {  // the accepted step's interpolant; y <- y1, f0 <- k7
-      const float dtc = ctl.fit_dt32;
-      for_owned([&](int64_t i) {
-        const float y1 = es[kEY1 * BD + i], fb = es[kEKl * BD + i];
-        float co[5];
-        dopri_fit(co, es[kEY * BD + i], y1, es[kEMid * BD + i], es[kEF0 * BD + i], fb, dtc);
-#pragma unroll
-        for (int q = 0; q < 5; ++q) es[(kECo + q) * BD + i] = co[q];
-        es[kEY * BD + i] = y1;
-        es[kEF0 * BD + i] = fb;
-      });
-    }
-    for (int j = ctl.io_lo; j < ctl.io_hi; ++j) {
-      const float xq = (float)((a.t[j] - ctl.t0s) / (ctl.t1s - ctl.t0s));
-      float* const so = a.sol + (int64_t)j * BD;
-      for_owned([&](int64_t i) {
-        float co[5];
-#pragma unroll
-        for (int q = 0; q < 5; ++q) co[q] = es[(kECo + q) * BD + i];
-        so[i] = dopri_eval(co, xq);
-      });
-    }
-    if (ctl.status >= 0) {
-      status = ctl.status;
-      break;
-    }
-    const int pw = (e + 1) & 1;
-    if (ctl.next == kNextProbe) {  // y0 + f0 h0 (fetode_lincomb with k[0] = f0)
-      const float hh = ctl.h0;
-      for_owned([&](int64_t i) { st_wt(a.xin + pw * BD + i, es[kEY * BD + i] + es[kEF0 * BD + i] * hh); });
-    } else if (ctl.next == kNextAttempt) {  // the attempt's running sums from f0, its first stage input
-      const float dtc = ctl.dt32;
-      for_owned([&](int64_t i) {
-        const float f0 = es[kEF0 * BD + i];
-        float a0 = 0.f;
-#pragma unroll
-        for (int q = 0; q < 6; ++q) {
-          const float v = f0 * (a.stc[0][q] * dtc);
-          es[(kEA + q) * BD + i] = v;
-          if (q == 0) a0 = v;
-        }
-        es[kEErr * BD + i] = f0 * (a.stc[0][6] * dtc);
-        es[kEMid * BD + i] = f0 * (a.stc[0][7] * dtc);
-        const float yi = es[kEY * BD + i] + a0;
-        st_wt(a.xin + pw * BD + i, yi);
-        es[kEY1 * BD + i] = yi;
-      });
-    }
-  }
-  const int nev = ctl.nev;
-  if (status != 4 && nev > 0) {
-    // the hysteresis memory after the solve: the last evaluation's layer inputs (ferro_class.py:409)
-    const int el = nev - 1, pl = el & 1;
-    const float* x0 = el == 0 ? a.y0 : a.xin + pl * BD;
-    const float* h0 = a.hs + (int64_t)pl * a.S0 * BH;
-    const int64_t nthr = (int64_t)G * kThreads;
-    const int64_t nmem = BH > BD ? BH : BD;   // either layer may be the wider one (D > H: 48 -> 16 -> 48)
-    for (int64_t j = (int64_t)blockIdx.x * kThreads + tid; j < nmem; j += nthr) {
-      if (j < BH) {
-        float v = h0[j];
-        for (int s = 1; s < a.S0; ++s) v = v + h0[s * BH + j];
-        a.st1[j] = v;
-      }
-      if (j < BD) a.st0[j] = x0[j];
-    }
-  }
-  if (blockIdx.x == 0 && tid == 0) {
-    a.stats[0] = ctl.nfev;
-    a.stats[1] = ctl.n_att;
-    a.stats[2] = __hip_atomic_load(a.bar + 64 * 9 + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) ? 4 : status;
-  }
-}
+#define WD_KERNEL wide_dopri5_kernel
+#define WD_TAPE false
+#define WD_WAVES 4
+#include "fetode_wide_dopri_body.h"
+#undef WD_KERNEL
+#undef WD_TAPE
+#undef WD_WAVES
+// the taped solve keeps its control state in registers (two waves per SIMD, one workgroup per CU:
+// a 256-VGPR budget, 195 used) — the
+// stores it adds would otherwise join the untaped kernel's control spills
+#define WD_KERNEL wide_dopri5_tape_kernel
+#define WD_TAPE true
+#define WD_WAVES 2, 2
+#include "fetode_wide_dopri_body.h"
+#undef WD_KERNEL
+#undef WD_TAPE
+#undef WD_WAVES
 
 struct WideDopriShape {
   int S0, S1, nT0, nT1, nOT0, nOT1;
@@ -2046,8 +1757,11 @@ int wide_dopri5_launch(const fetode_kanlinear_t* kan0, const fetode_ferro_t* fer
                        int64_t B, const float* prev0, const float* prev1, uint32_t reinit_mask, const double* t,
                        int32_t T, double rtol, double atol, const double* opts, const float* tableau, float* solution,
                        float* state0, float* state1, void* workspace, int32_t* stats, double* attempts,
-                       int32_t max_attempts, const fetode_xrank_t* xr, int64_t B_total, void* stream) {
+                       int32_t max_attempts, const fetode_xrank_t* xr, int64_t B_total, void* stream,
+                       bool taped = false, float* tape = nullptr, int64_t tape_cap = 0, double* init_rec = nullptr) {
   if (!kan0 || !fer0 || !kan1 || !fer1) return set_err(FETODE_EUNSUPPORTED, "wide dopri5: needs two KAN-FET layers");
+  if (taped && (tape_cap < 0 || (tape_cap > 0 && !tape) || !init_rec))
+    return set_err(FETODE_EINVAL, "wide dopri5 tape: null tape / init_rec");
   if (!wide_supported(kan0, fer0) || !wide_supported(kan1, fer1))
     return set_err(FETODE_EUNSUPPORTED, "wide dopri5: a layer has no wide kernel");
   const int D = kan0->in_features, H = kan0->out_features;
@@ -2064,7 +1778,8 @@ int wide_dopri5_launch(const fetode_kanlinear_t* kan0, const fetode_ferro_t* fer
   const WideDopriShape sh = wide_dopri_shape(B, D, H, exact ? B_total : 0);
   if ((int64_t)sh.nT0 * sh.S0 > 0x7fffffff / 2) return set_err(FETODE_EINVAL, "wide dopri5: batch too large");
   const int K = fer0->num_basis;
-  const void* fn = K == 12 ? (const void*)wide_dopri5_kernel<12> : (const void*)wide_dopri5_kernel<10>;
+  const void* fn = taped ? (K == 12 ? (const void*)wide_dopri5_tape_kernel<12> : (const void*)wide_dopri5_tape_kernel<10>)
+                         : (K == 12 ? (const void*)wide_dopri5_kernel<12> : (const void*)wide_dopri5_kernel<10>);
   // persistent grid: every workgroup resident at once (the phases meet at grid barriers)
   const int64_t resident = resident_wgs(fn, kThreads);
   if (resident < 0) return set_err(FETODE_EHIP, "wide dopri5: occupancy query failed");
@@ -2140,6 +1855,13 @@ int wide_dopri5_launch(const fetode_kanlinear_t* kan0, const fetode_ferro_t* fer
     a.xr_peers = (double* const*)xr->peers;
     a.xr_inbox = (double*)xr->inbox;
   }
+  if (taped) {  // planes x (cap, B, D) | h (cap, B, H) | k (cap, B, D)
+    a.tpx = tape;
+    a.tph = tape + tape_cap * B * D;
+    a.tpk = a.tph + tape_cap * B * H;
+    a.tape_cap = tape_cap;
+    a.init_rec = init_rec;
+  }
   hipStream_t s = (hipStream_t)stream;
   HIP_CHECK_RET(hipMemsetAsync(workspace, 0, sizeof(unsigned) * kWBarWords, s));
   void* args[] = {&a};
@@ -2169,6 +1891,18 @@ int fetode_wide_dopri5(const fetode_kanlinear_t* kan0, const fetode_ferro_t* fer
   return wide_dopri5_launch(kan0, fer0, plan0, kan1, fer1, plan1, y0, B, prev0, prev1, reinit_mask, t, T, rtol, atol,
                             opts, tableau, solution, state0, state1, workspace, stats, attempts, max_attempts, nullptr,
                             B, stream);
+}
+
+int fetode_wide_dopri5_tape(const fetode_kanlinear_t* kan0, const fetode_ferro_t* fer0, const void* plan0,
+                            const fetode_kanlinear_t* kan1, const fetode_ferro_t* fer1, const void* plan1, const float* y0,
+                            int64_t B, const float* prev0, const float* prev1, uint32_t reinit_mask, const double* t,
+                            int32_t T, double rtol, double atol, const double* opts, const float* tableau,
+                            float* solution, float* state0, float* state1, void* workspace, int32_t* stats,
+                            double* attempts, int32_t max_attempts, float* tape, int64_t tape_cap, double* init_rec,
+                            void* stream) {
+  return wide_dopri5_launch(kan0, fer0, plan0, kan1, fer1, plan1, y0, B, prev0, prev1, reinit_mask, t, T, rtol, atol,
+                            opts, tableau, solution, state0, state1, workspace, stats, attempts, max_attempts, nullptr,
+                            B, stream, true, tape, tape_cap, init_rec);
 }
 
 int fetode_wide_dopri5_xrank(const fetode_kanlinear_t* kan0, const fetode_ferro_t* fer0, const void* plan0,

@@ -832,6 +832,216 @@ def _try_ecg_resident_train(func, y0, tp, reversed_, rtol, atol, options):
         return None
 
 
+class _WideDopri5Fn(torch.autograd.Function):
+    """Training through the device-resident dopri5 solve of the two-layer wide KAN-FET field (the
+    reference's own training call: odeint(self.dynamics, z0, t_fut, method="dopri5") then
+    loss.backward(), train_kan_fet_ett.py:192, :312-335).  Forward: ONE launch
+    (fetode_wide_dopri5_tape) that also records every evaluation's layer inputs and output, the
+    attempt log and the initial-step scalars; the tape is sized from the module's previous solve
+    (func._fetode_wide_d5tape), and a longer solve is re-run from the saved memory with room.
+    Backward: fetode_wide_dopri5_backward, a sequence of launches without a read-back that walks the
+    attempts backwards and sums the parameter gradients over stacked (evaluation, row) chunks.
+    flat0 / flat1: each layer's parameters as one tensor (autograd_ops._flat_params), so each layer
+    gets its gradients back as one tensor."""
+
+    @staticmethod
+    def forward(ctx, func, field, y0, t_dev, rtol, atol, opts, ents, layouts, flat0, flat1):
+        from .autograd_ops import field_layers
+        lib = _lib.load()
+        (k0, f0), (k1, f1) = field_layers(field)
+        e0, e1 = ents
+        dev = y0.device
+        B, D = y0.shape
+        H = k0.out_features
+        T = t_dev.numel()
+
+        def mem(f, width):   # the first-call rule of FerroelectricBasis._needs_reinit (as _try_wide_resident)
+            p = f._prev
+            fresh = p.shape != (B, width) or p.device != dev or p.dtype != torch.float32
+            if not fresh and not p.is_contiguous():
+                p = f._prev = p.contiguous()
+            return fresh, p
+
+        re0, p0 = mem(f0, D)
+        re1, p1 = mem(f1, H)
+        # the memory before the solve: the reverse sweep's first memory; restored before a re-run / on a timeout
+        s0 = None if re0 else p0.clone()
+        s1 = None if re1 else p1.clone()
+        st0 = torch.empty(B, D, device=dev, dtype=torch.float32) if re0 else p0   # prev_x after the solve
+        st1 = torch.empty(B, H, device=dev, dtype=torch.float32) if re1 else p1
+        mask = (1 if re0 else 0) | (2 if re1 else 0)
+        per_ev = B * (2 * D + H)
+        cap, max_att = getattr(func, "_fetode_wide_d5tape", (256, 64))
+        cap, max_att = max(1, int(cap)), max(1, int(max_att))
+        sol = torch.empty(T, B, D, device=dev, dtype=torch.float32)
+        ws = torch.empty(max(1, lib.fetode_wide_dopri5_workspace(B, D, H) // 4), device=dev, dtype=torch.float32)
+        stats = torch.empty(3, device=dev, dtype=torch.int32)
+        init_rec = torch.zeros(5, device=dev, dtype=torch.float64)
+        by = _lib.ctypes.byref
+        optp = opts.ctypes.data_as(_lib.ctypes.POINTER(_lib.ctypes.c_double))
+        tabp = _TABLEAU.ctypes.data_as(_lib.ctypes.POINTER(_lib.ctypes.c_float))
+
+        def restore():
+            with torch.no_grad():
+                if s0 is not None:
+                    p0.copy_(s0)
+                if s1 is not None:
+                    p1.copy_(s1)
+
+        while True:
+            tape = torch.empty(cap * per_ev, device=dev, dtype=torch.float32)   # planes x | h | k
+            att = torch.empty(max_att, 4, device=dev, dtype=torch.float64)
+            rc = lib.fetode_wide_dopri5_tape(
+                by(e0[1]), by(e0[2]), e0[0].data_ptr(), by(e1[1]), by(e1[2]), e1[0].data_ptr(), y0.data_ptr(), B,
+                _lib.ptr(s0), _lib.ptr(s1), mask, t_dev.data_ptr(), T, rtol, atol, optp, tabp, sol.data_ptr(),
+                st0.data_ptr(), st1.data_ptr(), ws.data_ptr(), stats.data_ptr(), att.data_ptr(), max_att,
+                tape.data_ptr(), cap, init_rec.data_ptr(), _lib.stream_handle(dev))
+            if rc == _lib.FETODE_EUNSUPPORTED:
+                raise _WideDeclined()
+            _lib.check(rc, "fetode_wide_dopri5_tape")
+            nfev, n_att, status = stats.tolist()
+            if status == 4:
+                restore()   # a grid timeout leaves the pre-solve memory (as the inference path)
+            _raise_status(status, "fetode_wide_dopri5_tape: a grid barrier timed out (workgroups not co-resident); "
+                                  "the solution is invalid")
+            if nfev <= cap and n_att <= max_att:
+                break
+            restore()   # the tape ran out: the same solve again with room for all of it
+            cap, max_att = nfev + 12, n_att + 2
+            del tape, att   # freed before the larger ones are allocated
+            sweep = lib.fetode_wide_dopri5_backward_workspace(by(e0[1]), by(e0[2]), by(e1[1]), by(e1[2]), B, max_att)
+            if sweep < 0 or cap * per_ev * 4 + sweep > _WIDE_RESIDENT_TRAIN[1]:
+                # the solve needs more than set_resident_wide_training's budget: the memory is the
+                # pre-solve one again, and the caller takes the host path (at once from the next call on)
+                func._fetode_wide_d5tape = (cap, max_att)
+                raise _WideDeclined()
+        func._fetode_wide_d5tape = (nfev + max(12, nfev // 8), n_att + max(2, n_att // 8))
+        if re0:
+            f0._prev = st0
+        if re1:
+            f1._prev = st1
+        dopri5_solve.last = ResidentSolve(stats, att)
+        ctx.field, ctx.ents, ctx.layouts, ctx.B, ctx.mask, ctx.cap = field, ents, layouts, B, mask, cap
+        ctx.t_dev, ctx.rtol, ctx.atol, ctx.opts = t_dev, rtol, atol, opts
+        ctx.n_ev, ctx.n_att = nfev, n_att
+        ctx.has = (s0 is not None, s1 is not None)
+        keep = [t for t in (s0, s1) if t is not None]
+        ctx.save_for_backward(tape, att, init_rec, *keep)
+        return sol
+
+    @staticmethod
+    def backward(ctx, grad):
+        from .autograd_ops import FERRO_PARAM_NAMES, field_layers, kan_params
+        lib = _lib.load()
+        tape, att, init_rec, *keep = ctx.saved_tensors
+        it = iter(keep)
+        s0 = next(it) if ctx.has[0] else None
+        s1 = next(it) if ctx.has[1] else None
+        B = ctx.B
+        dev = grad.device
+        g = _lib.f32c(grad)
+        e0, e1 = ctx.ents
+        gy0 = torch.empty(B, g.shape[-1], device=dev, dtype=torch.float32) if ctx.needs_input_grad[2] else None
+        gflat, structs = [], []
+        for l, (kan, fer) in enumerate(field_layers(ctx.field)):
+            offs, total = ctx.layouts[l]
+            if not ctx.needs_input_grad[9 + l]:
+                gflat.append(None)
+                structs += [None, None]
+                continue
+            gf = torch.zeros(total, device=dev, dtype=torch.float32)
+            kp = kan_params(kan)
+            fp = [getattr(fer, n) for n in FERRO_PARAM_NAMES]
+            views = iter([gf.narrow(0, o, p.numel()) for o, p in zip(offs, [p for p in kp if p is not None] + fp)])
+            kg = _lib.KANLinearGrad(*[None if p is None else next(views).data_ptr() for p in kp])
+            fg = _lib.FerroGrad(*[next(views).data_ptr() for _ in fp])
+            gflat.append(gf)
+            structs += [kg, fg]
+        by = _lib.ctypes.byref
+        nbytes = lib.fetode_wide_dopri5_backward_workspace(by(e0[1]), by(e0[2]), by(e1[1]), by(e1[2]), B, ctx.n_att)
+        if nbytes < 0:
+            _lib.check(_lib.FETODE_EUNSUPPORTED, "fetode_wide_dopri5_backward_workspace")
+        ws = torch.empty(max(1, nbytes // 4), device=dev, dtype=torch.float32)
+        _lib.check(lib.fetode_wide_dopri5_backward(
+            by(e0[1]), by(e0[2]), e0[0].data_ptr(), by(e1[1]), by(e1[2]), e1[0].data_ptr(), B, _lib.ptr(s0),
+            _lib.ptr(s1), ctx.mask, ctx.t_dev.data_ptr(), ctx.t_dev.numel(), ctx.rtol, ctx.atol,
+            ctx.opts.ctypes.data_as(_lib.ctypes.POINTER(_lib.ctypes.c_double)),
+            _TABLEAU.ctypes.data_as(_lib.ctypes.POINTER(_lib.ctypes.c_float)), g.data_ptr(), tape.data_ptr(), ctx.cap,
+            ctx.n_ev, att.data_ptr(), ctx.n_att, init_rec.data_ptr(), _lib.ptr(gy0),
+            *[None if s is None else by(s) for s in structs], ws.data_ptr(), _lib.stream_handle(dev)),
+            "fetode_wide_dopri5_backward")
+        return (None, None, gy0, None, None, None, None, None, None, gflat[0], gflat[1])
+
+
+class _WideDeclined(Exception):
+    """fetode_wide_dopri5_tape refused the launch (FETODE_EUNSUPPORTED, nothing written), or the solve
+    outgrew the tape budget (the pre-solve memory restored)."""
+
+
+_WIDE_RESIDENT_TRAIN = [os.environ.get("FETODE_WIDE_DOPRI5_TAPE", "0") == "1", 16 << 30]
+
+
+def set_resident_wide_training(enabled: bool, tape_bytes=None) -> bool:
+    """Route dopri5 training solves of the two-layer wide KAN-FET fields (ett.KANFETDynamics) through
+    the taped resident solve + the device reverse sweep, or (default) through _Dopri5Grad
+    (host-driven autograd).  Also env FETODE_WIDE_DOPRI5_TAPE=1.  ``tape_bytes``: the most device
+    memory the tape and one chunk's gradient tape may take (default 16 GiB; the tape holds
+    (2 D + H) floats per trajectory and evaluation — about 6 GB for the reference's iteration at
+    rtol 1e-7); a solve expected to need more (by the module's previous solve, or found to once its
+    first, short tape has overflowed) takes _Dopri5Grad.  Returns the previous value."""
+    prev = _WIDE_RESIDENT_TRAIN[0]
+    _WIDE_RESIDENT_TRAIN[0] = bool(enabled)
+    if tape_bytes is not None:
+        _WIDE_RESIDENT_TRAIN[1] = int(tape_bytes)
+    return prev
+
+
+def _try_wide_resident_train(func, y0, tp, reversed_, rtol, atol, options):
+    """The taped resident solve + reverse sweep when `func` is a tagged two-layer wide KAN-FET field
+    (the shape tests of _try_wide_resident), every parameter of it requires gradients, the solve is
+    single-device (no norm_group), forward in time with scalar tolerances and options, no noise and
+    the constant branch sign, and the tape fits the budget of set_resident_wide_training; None
+    otherwise (the caller's host path).  (odeint detaches t before any solver sees it: no path
+    differentiates the output times.)  _WIDE_RESIDENT_GAP does
+    not apply: it is the inference crossover against the host loop without autograd."""
+    from .autograd_ops import FERRO_PARAM_NAMES, _flat_params, field_layers, kan_params, wide_plan
+    from .odeint import fused_field
+    field = fused_field(func)
+    if field is None or not _scalar_request(y0, reversed_, rtol, atol, options):   # norm_group is no scalar option
+        return None
+    if not getattr(field, "has_ferro", False):
+        return None
+    layers = field_layers(field)
+    if len(layers) != 2 or any(f is None or f._bsign is not None or f.use_noise for _, f in layers):
+        return None
+    (k0, f0), (k1, f1) = layers
+    B, D = y0.shape
+    H = k0.out_features
+    dev = y0.device
+    if B <= 0 or D != k0.in_features or k1.in_features != H or k1.out_features != D or f0.num_basis != f1.num_basis:
+        return None
+    ps = [[p for p in kan_params(k) if p is not None] + [getattr(f, n) for n in FERRO_PARAM_NAMES] for k, f in layers]
+    if not all(p.requires_grad for l in ps for p in l):
+        return None
+    e0, e1 = wide_plan(k0, f0, dev), wide_plan(k1, f1, dev)
+    if e0 is None or e1 is None:
+        return None
+    lib = _lib.load()
+    by = _lib.ctypes.byref
+    cap, n_att = getattr(func, "_fetode_wide_d5tape", (256, 64))
+    sweep = lib.fetode_wide_dopri5_backward_workspace(by(e0[1]), by(e0[2]), by(e1[1]), by(e1[2]), B, max(1, int(n_att)))
+    if sweep < 0 or lib.fetode_wide_dopri5_workspace(B, D, H) < 0:
+        return None
+    if max(1, int(cap)) * B * (2 * D + H) * 4 + sweep > _WIDE_RESIDENT_TRAIN[1]:
+        return None
+    (flat0, lay0), (flat1, lay1) = _flat_params(k0, f0, ps[0]), _flat_params(k1, f1, ps[1])
+    try:
+        return _WideDopri5Fn.apply(func, field, y0.to(torch.float32).contiguous(), _t_device(tp, dev), float(rtol),
+                                   float(atol), _opts_array(options), (e0, e1), (lay0, lay1), flat0, flat1)
+    except _WideDeclined:
+        return None
+
+
 def _try_wide_resident(func, y0, tp, reversed_, rtol, atol, options):
     """The whole solve in one launch (fetode_wide_dopri5) when `func` is a tagged two-layer wide
     KAN-FET field — the ETT forecaster's KANFETDynamics, KANFET([latent, hidden, latent]),
@@ -1313,6 +1523,10 @@ def dopri5_solve(func, y0, tc, tp, reversed_, rtol, atol, options):
     if _needs_grad(func, y0):
         if _RESIDENT and _ECG_RESIDENT_TRAIN:
             sol = _try_ecg_resident_train(func, y0, tp, reversed_, rtol, atol, options)
+            if sol is not None:
+                return sol
+        if _RESIDENT and _WIDE_RESIDENT_TRAIN[0]:
+            sol = _try_wide_resident_train(func, y0, tp, reversed_, rtol, atol, options)
             if sol is not None:
                 return sol
         if _RESIDENT and _RESIDENT_TRAIN:

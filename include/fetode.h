@@ -267,6 +267,56 @@ int fetode_wide_dopri5(const fetode_kanlinear_t* kan0, const fetode_ferro_t* fer
                        int32_t* stats, double* attempts, int32_t max_attempts, void* stream);
 int64_t fetode_wide_dopri5_workspace(int64_t B, int32_t D, int32_t H);
 
+/* Training through the wide field's resident dopri5 solve (train_kan_fet_ett.py:192 then :312-335:
+ * the forecaster's odeint(..., method="dopri5") followed by loss.backward()).
+ * _tape: fetode_wide_dopri5 that also records, for the first tape_cap evaluations, three planes
+ *   tape = x (tape_cap, B, D) | h (tape_cap, B, H) | k (tape_cap, B, D)
+ * (the layer-0 input, the hidden, the output of evaluation e; planes rather than the LV tape's
+ * (tape_cap, B, 2 D + H) rows, so that consecutive evaluations of one plane are the stacked rows the
+ * wide VJPs take), the attempt log, and the initial-step scalars {d0, d1, d2, h0, h1} (init_rec, 5
+ * doubles).  Evaluation 0 is f(y0), 1 the initial-step probe (absent with first_step), then six per
+ * attempt, rejected ones included; the hysteresis memory of evaluation e is x_{e-1} / h_{e-1}
+ * (prev0 / prev1 or the first-call rule for e = 0), so the tape alone reproduces every gate.  The
+ * tape adds stores only: attempts, nfev, solution and final state are bitwise fetode_wide_dopri5's.
+ * The caller checks stats[0] (nfev) <= tape_cap and stats[1] <= max_attempts (else re-runs from the
+ * same memory with larger buffers).
+ * _backward: the reverse sweep, an ordinary sequence of launches on `stream` (no persistent kernel,
+ * no grid barrier, no host synchronisation): the attempts walked backwards — every evaluation of
+ * every attempt through the wide VJPs, the stage sums, the error norm, _optimal_step_size,
+ * _select_initial_step and the dense output, the control chain (dt, ratio, t) in fp64 on the
+ * device.  kan*, ferro*, plan*, prev*, reinit_mask, t, rtol / atol / opts / tableau: the forward's
+ * (prev* = the memory BEFORE the solve); grad_solution (T, B, D); tape / tape_cap / attempts /
+ * init_rec: the forward's records; n_ev = stats[0], n_att = stats[1] (n_ev = base + 6 n_att).
+ * Outputs (nullable), written not accumulated: grad_y0 (B, D); per layer a fetode_kanlinear_grad_t
+ * and a fetode_ferro_grad_t.  The parameter sums run over chunks of whole attempts of about
+ * FETODE_WIDE_BWD_ROWS (env, default 8192) stacked (evaluation, row) samples: chunks are counted
+ * from the last attempt and added latest first, each by one call per layer of
+ * fetode_ferro_backward_wide / fetode_kanlinear_backward_wide (fetode_kanlinear_backward where the
+ * output width has no wide VJP) in that kernel's fixed order; then the probe and evaluation 0.  No
+ * atomics: the same inputs give the same bits.  workspace: fetode_wide_dopri5_backward_workspace
+ * bytes.  Replaces: autograd through the host-driven loop (dopri5.py _Dopri5Grad). */
+typedef struct fetode_kanlinear_grad fetode_kanlinear_grad_t; /* defined with the VJPs below */
+typedef struct fetode_ferro_grad fetode_ferro_grad_t;
+int fetode_wide_dopri5_tape(const fetode_kanlinear_t* kan0, const fetode_ferro_t* ferro0, const void* plan0,
+                            const fetode_kanlinear_t* kan1, const fetode_ferro_t* ferro1, const void* plan1,
+                            const float* y0, int64_t B, const float* prev0, const float* prev1,
+                            uint32_t reinit_mask, const double* t, int32_t T, double rtol, double atol,
+                            const double* opts, const float* tableau, float* solution, float* state0,
+                            float* state1, void* workspace, int32_t* stats, double* attempts,
+                            int32_t max_attempts, float* tape, int64_t tape_cap, double* init_rec, void* stream);
+int64_t fetode_wide_dopri5_backward_workspace(const fetode_kanlinear_t* kan0, const fetode_ferro_t* ferro0,
+                                              const fetode_kanlinear_t* kan1, const fetode_ferro_t* ferro1,
+                                              int64_t B, int32_t n_att);
+int fetode_wide_dopri5_backward(const fetode_kanlinear_t* kan0, const fetode_ferro_t* ferro0, const void* plan0,
+                                const fetode_kanlinear_t* kan1, const fetode_ferro_t* ferro1, const void* plan1,
+                                int64_t B, const float* prev0, const float* prev1, uint32_t reinit_mask,
+                                const double* t, int32_t T, double rtol, double atol, const double* opts,
+                                const float* tableau, const float* grad_solution, const float* tape,
+                                int64_t tape_cap, int32_t n_ev, const double* attempts, int32_t n_att,
+                                const double* init_rec, float* grad_y0, const fetode_kanlinear_grad_t* kan_grad0,
+                                const fetode_ferro_grad_t* ferro_grad0, const fetode_kanlinear_grad_t* kan_grad1,
+                                const fetode_ferro_grad_t* ferro_grad1, void* workspace, void* stream);
+
 /* The whole dopri5 solve of a fused-shape field (the LV KAN / KAN-FET [2,10,2] fields) in ONE
  * cooperative launch — torchdiffeq's default method of every reference odeint without `method`
  * (train_kanfet_node_predprey.py:252,260, rtol 1e-7 / atol 1e-9): f0, misc._select_initial_step
