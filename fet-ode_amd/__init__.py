@@ -6,6 +6,8 @@ Drop-in surface of the reference hot path (sallywang147/FET-ODE):
   * ``ferro_class``          — FerroelectricBasis
   * ``ecg``                  — the ECG KAN-FET NODE (hysteretic LogisticBasis, KANFeatureMixer,
                                No_MLP_KANODEFunc, KanFet_NODE; train_ecg_kan_fet_nn_ode.py)
+                               and the input-driven ECG NODE-RNN (LinearInterp1D, InputDrivenKANODEFunc,
+                               OneODEEncoder, FullyNonlinearKANCell, NODE_RNN; compare_noise_ecg.py)
   * ``mnist``                — the MNIST Kuramoto + KANLinear classifier (mnist_kuramoto_kan.py)
   * ``ett``                  — odeint_rk4, EnergyWindowDataset, the KAN-FET LatentNeuralODEForecaster
                                and the KAN-RNN encoder (KANRNNEncoder, FullyNonlinearKANCell,

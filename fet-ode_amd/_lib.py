@@ -296,6 +296,19 @@ SIGNATURES = {
     "fetode_logistic_basis_backward_workspace": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64]),
     "fetode_logistic_basis_backward": (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, _vp, _vp,
                                                       _vp, _vp, _vp, _vp, _vp, _vp]),
+    "fetode_driven_supported": (ctypes.c_int, [ctypes.POINTER(FerroDesc)]),
+    "fetode_driven_set_spw": (ctypes.c_int, [ctypes.c_int]),
+    "fetode_driven_plan_bytes": (ctypes.c_int64, [ctypes.POINTER(FerroDesc)]),
+    "fetode_driven_plan_build": (ctypes.c_int, [ctypes.POINTER(FerroDesc), _vp, _vp, _vp, _vp]),
+    "fetode_driven_table": (ctypes.c_int, [_vp, ctypes.c_int64, _vp, ctypes.c_int32, _vp, ctypes.c_int64,
+                                           ctypes.c_int32, _vp, _vp]),
+    "fetode_driven_fixed": (ctypes.c_int, [ctypes.POINTER(FerroDesc), _vp, ctypes.c_int32, _vp, ctypes.c_int64, _vp,
+                                           ctypes.c_int64, ctypes.c_int64, _vp, ctypes.c_int32, _vp, _vp, _vp, _vp]),
+    "fetode_driven_fixed_tape": (ctypes.c_int, [ctypes.POINTER(FerroDesc), _vp, ctypes.c_int32, _vp, ctypes.c_int64,
+                                                _vp, ctypes.c_int64, ctypes.c_int64, _vp, ctypes.c_int32, _vp, _vp,
+                                                _vp, _vp, _vp, _vp]),
+    "fetode_driven_fixed_backward": (ctypes.c_int, [ctypes.POINTER(FerroDesc), _vp, ctypes.c_int32, ctypes.c_int64,
+                                                    _vp, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 _lib: Optional[ctypes.CDLL] = None

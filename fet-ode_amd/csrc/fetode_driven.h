@@ -1,0 +1,53 @@
+// fetode_driven.h — the input-driven Ferro field of the ECG NODE-RNN encoder
+// (compare_noise_ecg.py:875-907):   dh/dt = tanh(Ferro_{(H+D)->H}(cat[h, x(t)])) * gain + bias.
+// Plan layout and launch arguments shared by the kernels of fetode_driven.hip.
+#pragma once
+#include <stdint.h>
+
+namespace fetode {
+
+// admitted family (fetode_driven_supported): D = in_dim - out_dim
+constexpr int kDrvHMax = 64;    // one lane per output
+constexpr int kDrvDMax = 4;
+constexpr int kDrvKMax = 16;
+constexpr int kDrvInMax = kDrvHMax + kDrvDMax;
+constexpr int kDrvThreads = 256;  // four waves: lane -> output o, wave -> inputs i = wave (mod 4)
+
+// Plan (floats): In*K*H elements of 4 constants, element (i, k, o) at ((i*K + k)*H + o)*4 so that
+// the 64 lanes of a wave (o) read consecutive 16-byte words:
+//   .x  gate_slope*log2e*Ec     .y  2*log2e*k     .z  2*log2e*k*Ec     .w  coef*Ps
+// then fconst[H] = sum_i (sum_k bias*coef), gain[H], bias[H].
+constexpr int64_t drv_plan_elems(int In, int H, int K) { return (int64_t)In * K * H; }
+constexpr int64_t drv_plan_floats(int In, int H, int K) { return 4 * drv_plan_elems(In, H, K) + 3 * (int64_t)H; }
+
+struct DrivenArgs {
+  const float* plan;
+  const float* h0;       // (B, H)
+  const float* u;        // (n_eval, B, D) driving table
+  const float* dt;       // (n_steps) fp32 step sizes of the steps this launch takes
+  const float* prev0;    // (B, H+D) hysteresis input before the first evaluation, null: zeros
+  float* sol;            // (n_steps, B, H) the state after every step
+  float* prev_out;       // (B, H+D) nullable: the last evaluation's input
+  float* tape_hx;        // (n_eval, B, H+D) taped kernels only
+  float* tape_phi;       // (n_eval, B, H)
+  int64_t B;
+  int64_t eval0;         // first evaluation (row of u / the tape) of this launch
+  int32_t H, D, K, n_steps;
+  float gs, gsl2e, wc;   // gate_slope, gate_slope*log2e, -2(1-alpha)
+};
+
+struct DrivenAdjArgs {
+  const float* plan;
+  const float* dt;        // (n_steps)
+  const float* prev0;     // (B, H+D) nullable
+  const float* tape_hx;   // (4 n_steps, B, H+D)
+  const float* tape_phi;  // (4 n_steps, B, H)
+  const float* grad_sol;  // (n_steps + 1, B, H): d loss / d every trajectory row, row 0 = h0
+  float* adj;             // (4 n_steps, B, H): d loss / d every evaluation's output
+  float* grad_h0;         // (B, H)
+  int64_t B;
+  int32_t H, D, K, n_steps;
+  float gs, gsl2e, wc;
+};
+
+}  // namespace fetode

@@ -1,0 +1,508 @@
+// fetode_driven.hip — the input-driven Ferro field of the ECG NODE-RNN encoder, solved in one launch
+// (compare_noise_ecg.py:848-946: LinearInterp1D, InputDrivenKANODEFunc, OneODEEncoder):
+//     dh/dt = tanh(Ferro_{(H+D)->H}(cat[h, x(t)])) * gain + bias          (torchdiffeq rk4, 3/8 rule)
+//   driven_table_kernel   x(t) at every evaluation time, the reference's fp32 expression (:861-872)
+//   driven_plan_kernel    per-element constants + sum bias*coef per output, one launch
+//   driven_fixed_kernel   the whole fixed-grid solve; a workgroup owns its samples from h0 to the end
+//   driven_adj_kernel     the reverse sweep along the chain of evaluations (d/dh only)
+// The reference resets the hysteresis state before every sample's solve, so the samples are
+// independent: sample b carries its own driving row and its own prev.  branch_sign stays 1, so
+//     m = 1 - 2(1-alpha)(1-u) sigma(gs(-x-Ec)),   u = sigma(gs(x - prev))       (DESIGN §3 "Algebra").
+// Mapping: 256 threads = 4 waves; lane -> output o (lanes >= H idle), wave w -> inputs i = w (mod 4).
+// Every lane sums the K bases of one input first, then its inputs; the four waves'
+// partial sums meet in LDS in a fixed order.  No workgroup waits on another one.
+#include "fetode_common.h"
+#include "fetode_driven.h"
+
+using namespace fetode;
+
+namespace {
+
+constexpr float kThird = 1.0f / 3.0f;
+
+// ---------------------------------------------------------------------------------------------
+// driving table: u[e][b][d] = LinearInterp1D(t_grid, x[b])(tq[e])
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void driven_table_kernel(const float* __restrict__ tq, int64_t n_eval,
+                                                          const float* __restrict__ tg, int T,
+                                                          const float* __restrict__ x, int64_t B, int D,
+                                                          float* __restrict__ u) {
+  const int64_t n = n_eval * B * D;
+  for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < n; idx += (int64_t)gridDim.x * blockDim.x) {
+    const int d = (int)(idx % D);
+    const int64_t b = (idx / D) % B, e = idx / ((int64_t)D * B);
+    const float lo = tg[0], hi = tg[T - 1];
+    float t = tq[e];
+    t = t < lo ? lo : (t > hi ? hi : t);                 // torch.clamp(t, t[0], t[-1])
+    int i = 0;                                           // searchsorted, left: #{grid < t}
+    for (int j = 0; j < T; ++j) i += tg[j] < t ? 1 : 0;
+    i = i < 1 ? 1 : (i > T - 1 ? T - 1 : i);             // .clamp(1, T - 1)
+    const float t0 = tg[i - 1], t1 = tg[i];
+    const float x0 = x[(b * T + (i - 1)) * D + d], x1 = x[(b * T + i) * D + d];
+    const float w = (t - t0) / ((t1 - t0) + 1e-12f);
+    u[idx] = (1.0f - w) * x0 + w * x1;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// plan
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void driven_plan_kernel(fetode_ferro_t fl, const float* __restrict__ gain,
+                                                         const float* __restrict__ bias, float* __restrict__ plan) {
+  const int In = fl.in_dim, H = fl.out_dim, K = fl.num_basis;
+  const int64_t ne = drv_plan_elems(In, H, K);
+  const float gsl2e = (float)fl.gate_slope * FETODE_LOG2E;
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  for (int64_t p = t; p < ne; p += (int64_t)gridDim.x * blockDim.x) {
+    const int o = (int)(p % H), k = (int)((p / H) % K), i = (int)(p / ((int64_t)H * K));
+    const int e = (i * H + o) * K + k;
+    const float Ec = fl.Ec[e], kk = fl.k[e];
+    const float k2 = 2.0f * FETODE_LOG2E * kk;
+    reinterpret_cast<float4*>(plan)[p] = make_float4(gsl2e * Ec, k2, k2 * Ec, fl.coef[e] * fl.Ps[e]);
+  }
+  if (t < H) {
+    const int o = (int)t;
+    float acc = 0.f;
+    for (int i = 0; i < In; ++i) {
+      float acc_i = 0.f;
+      for (int k = 0; k < K; ++k) {
+        const int e = (i * H + o) * K + k;
+        acc_i += fl.bias[e] * fl.coef[e];
+      }
+      acc += acc_i;
+    }
+    float* tail = plan + 4 * ne;
+    tail[o] = acc;
+    tail[H + o] = gain[o];
+    tail[2 * H + o] = bias[o];
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// forward solve
+// ---------------------------------------------------------------------------------------------
+template <int S, int KT, bool TAPE>
+__global__ __launch_bounds__(kDrvThreads) void driven_fixed_kernel(DrivenArgs a) {
+  __shared__ float xs[S][kDrvInMax], gxs[S][kDrvInMax], vs[S][kDrvInMax];
+  __shared__ float part[4][S][64];
+  const int H = a.H, D = a.D, In = H + D, K = KT > 0 ? KT : a.K;
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int64_t B = a.B, b0 = (int64_t)blockIdx.x * S;
+  const float4* __restrict__ el = reinterpret_cast<const float4*>(a.plan);
+  const float* __restrict__ tail = a.plan + 4 * drv_plan_elems(In, H, K);
+  const bool own = wv == 0 && lane < H;               // holds h and the stage slopes of output `lane`
+  const int ds = (tid - 64) / D, dd = (tid - 64) - ds * D;
+  const bool drv = tid >= 64 && tid < 64 + S * D;     // publishes driving input dd of sample ds
+  const float gs = a.gs, gsl2e = a.gsl2e, wc = a.wc;
+  float fcon = 0.f, gain = 0.f, bias = 0.f;
+  if (own) {
+    fcon = tail[lane];
+    gain = tail[H + lane];
+    bias = tail[2 * H + lane];
+  }
+  // input i of sample s for the next evaluation: value, its gate against the previous evaluation's
+  // input (prev <- hx, call order) and the per-input factors of the element loop
+  auto publish = [&](int s, int i, float xn, float xo) {
+    const float up = 1.0f / (1.0f + expf(-(gs * (xn - xo))));
+    xs[s][i] = xn;
+    gxs[s][i] = gsl2e * xn;
+    vs[s][i] = wc * (1.0f - up);
+  };
+  float h[S], k1[S], k2[S], k3[S];
+#pragma unroll
+  for (int s = 0; s < S; ++s) {
+    h[s] = k1[s] = k2[s] = k3[s] = 0.f;
+    const int64_t b = b0 + s;
+    if (own) {
+      const bool live = b < B;
+      h[s] = live ? a.h0[b * H + lane] : 0.f;
+      publish(s, lane, h[s], (live && a.prev0) ? a.prev0[b * In + lane] : 0.f);
+    }
+  }
+  if (drv) {
+    const int64_t b = b0 + ds;
+    const bool live = b < B;
+    publish(ds, H + dd, live ? a.u[(a.eval0 * B + b) * D + dd] : 0.f,
+            (live && a.prev0) ? a.prev0[b * In + H + dd] : 0.f);
+  }
+  const int n_eval = 4 * a.n_steps;
+  for (int e = 0; e < n_eval; ++e) {
+    const int st = e & 3, step = e >> 2;
+    const int64_t ge = a.eval0 + e;
+    __syncthreads();  // this evaluation's inputs are published
+    if (TAPE) {
+      for (int idx = tid; idx < S * In; idx += kDrvThreads) {
+        const int s = idx / In, i = idx - s * In;
+        if (b0 + s < B) a.tape_hx[(ge * B + b0 + s) * In + i] = xs[s][i];
+      }
+    }
+    float acc[S];
+#pragma unroll
+    for (int s = 0; s < S; ++s) acc[s] = 0.f;
+    if (lane < H) {
+      for (int i = wv; i < In; i += 4) {
+        float x[S], gx[S], v[S], ai[S];
+#pragma unroll
+        for (int s = 0; s < S; ++s) {
+          x[s] = xs[s][i];
+          gx[s] = gxs[s][i];
+          v[s] = vs[s][i];
+          ai[s] = 0.f;
+        }
+        const float4* __restrict__ p = el + (int64_t)i * K * H + lane;
+#pragma unroll KT > 0 ? KT : 1
+        for (int k = 0; k < K; ++k) {
+          const float4 c = p[(int64_t)k * H];
+#pragma unroll
+          for (int s = 0; s < S; ++s) {
+            const float cn = rcp(1.0f + ex2(gx[s] + c.x));         // sigma(gs(-x - Ec))
+            const float m = ffma(v[s], cn, 1.0f);
+            const float z = ffma(c.z, m, c.y * x[s]);              // 2 log2e k (x + Ec m)
+            const float th = ffma(rcp(1.0f + ex2(z)), -2.0f, 1.0f);  // tanh(k (x + Ec m))
+            ai[s] = ffma(c.w, th, ai[s]);
+          }
+        }
+#pragma unroll
+        for (int s = 0; s < S; ++s) acc[s] += ai[s];
+      }
+    }
+#pragma unroll
+    for (int s = 0; s < S; ++s) part[wv][s][lane] = acc[s];
+    __syncthreads();  // partial sums are in; nobody reads this evaluation's inputs any more
+    const bool last = e == n_eval - 1;
+    if (own) {
+      const float dt = a.dt[step];
+#pragma unroll
+      for (int s = 0; s < S; ++s) {
+        const int64_t b = b0 + s;
+        const bool live = b < B;
+        const float phi = ((part[0][s][lane] + part[1][s][lane]) + (part[2][s][lane] + part[3][s][lane])) + fcon;
+        if (TAPE && live) a.tape_phi[(ge * B + b) * H + lane] = phi;
+        const float f = tanhf(phi) * gain + bias;
+        float xn;  // torchdiffeq rk4_alt_step_func, its op order
+        if (st == 0) {
+          k1[s] = f;
+          xn = h[s] + (dt * f) * kThird;
+        } else if (st == 1) {
+          k2[s] = f;
+          xn = h[s] + dt * (f - k1[s] * kThird);
+        } else if (st == 2) {
+          k3[s] = f;
+          xn = h[s] + dt * ((k1[s] - k2[s]) + f);
+        } else {
+          xn = h[s] + (((k1[s] + 3.0f * (k2[s] + k3[s])) + f) * dt) * 0.125f;
+          h[s] = xn;
+          if (live) a.sol[((int64_t)step * B + b) * H + lane] = xn;
+        }
+        if (!last) publish(s, lane, xn, xs[s][lane]);
+      }
+    }
+    if (drv && !last) {
+      const int64_t b = b0 + ds;
+      publish(ds, H + dd, b < B ? a.u[((ge + 1) * B + b) * D + dd] : 0.f, xs[ds][H + dd]);
+    }
+  }
+  // prev <- the last evaluation's input (still in xs: the last evaluation publishes nothing)
+  if (a.prev_out && n_eval > 0) {
+    for (int idx = tid; idx < S * In; idx += kDrvThreads) {
+      const int s = idx / In, i = idx - s * In;
+      if (b0 + s < B) a.prev_out[(b0 + s) * In + i] = xs[s][i];
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// reverse sweep: adjoints of every evaluation's output and of h0; the gate reads prev detached
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+  return v;
+}
+
+template <int S, int KT>
+__global__ __launch_bounds__(kDrvThreads) void driven_adj_kernel(DrivenAdjArgs a) {
+  __shared__ float xs[S][kDrvHMax], gxs[S][kDrvHMax], vs[S][kDrvHMax], us[S][kDrvHMax];
+  __shared__ float gph[S][64], gout[S][kDrvHMax];
+  const int H = a.H, D = a.D, In = H + D, K = KT > 0 ? KT : a.K;
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int64_t B = a.B, b0 = (int64_t)blockIdx.x * S;
+  const float4* __restrict__ el = reinterpret_cast<const float4*>(a.plan);
+  const float* __restrict__ tail = a.plan + 4 * drv_plan_elems(In, H, K);
+  const bool own = wv == 0 && lane < H;
+  const float gs = a.gs, gsl2e = a.gsl2e, wc = a.wc;
+  const float gain = own ? tail[H + lane] : 0.f;
+  const int n_steps = a.n_steps;
+  float lam[S], ay[S], ak1[S], ak2[S], ak3[S], ak4[S];
+#pragma unroll
+  for (int s = 0; s < S; ++s) {
+    const int64_t b = b0 + s;
+    lam[s] = (own && b < B) ? a.grad_sol[((int64_t)n_steps * B + b) * H + lane] : 0.f;
+    ay[s] = ak1[s] = ak2[s] = ak3[s] = ak4[s] = 0.f;
+  }
+  for (int e = 4 * n_steps - 1; e >= 0; --e) {
+    const int st = e & 3, step = e >> 2;
+    const float dt = a.dt[step];
+    if (own) {
+#pragma unroll
+      for (int s = 0; s < S; ++s) {
+        const int64_t b = b0 + s;
+        const bool live = b < B;
+        if (st == 3) {  // y1 = y + ((k1 + 3 (k2 + k3)) + k4) dt / 8
+          ay[s] = lam[s];
+          ak1[s] = ak4[s] = (lam[s] * dt) * 0.125f;
+          ak2[s] = ak3[s] = 3.0f * ((lam[s] * dt) * 0.125f);
+        }
+        float ae = ak1[s];   // plain selects of values: no pointer select over the register arrays
+        if (st == 1) ae = ak2[s];
+        if (st == 2) ae = ak3[s];
+        if (st == 3) ae = ak4[s];
+        float g = 0.f;
+        if (live) {
+          a.adj[((int64_t)e * B + b) * H + lane] = ae;
+          const float t = tanhf(a.tape_phi[((int64_t)e * B + b) * H + lane]);
+          g = (ae * gain) * (1.0f - t * t);
+        }
+        gph[s][lane] = g;
+      }
+    } else if (wv == 0) {
+#pragma unroll
+      for (int s = 0; s < S; ++s) gph[s][lane] = 0.f;
+    }
+    for (int idx = tid; idx < S * H; idx += kDrvThreads) {
+      const int s = idx / H, i = idx - s * H;
+      const int64_t b = b0 + s;
+      float xv = 0.f, pv = 0.f;
+      if (b < B) {
+        xv = a.tape_hx[((int64_t)e * B + b) * In + i];
+        pv = e > 0 ? a.tape_hx[((int64_t)(e - 1) * B + b) * In + i] : (a.prev0 ? a.prev0[b * In + i] : 0.f);
+      }
+      const float up = 1.0f / (1.0f + expf(-(gs * (xv - pv))));
+      xs[s][i] = xv;
+      gxs[s][i] = gsl2e * xv;
+      vs[s][i] = wc * (1.0f - up);
+      us[s][i] = up;
+    }
+    __syncthreads();
+    float gp[S];
+#pragma unroll
+    for (int s = 0; s < S; ++s) gp[s] = gph[s][lane];
+    for (int i = wv; i < H; i += 4) {   // only the h inputs carry an adjoint
+      float d[S];
+#pragma unroll
+      for (int s = 0; s < S; ++s) d[s] = 0.f;
+      if (lane < H) {
+        const float4* __restrict__ p = el + (int64_t)i * K * H + lane;
+#pragma unroll KT > 0 ? KT : 1
+        for (int k = 0; k < K; ++k) {
+          const float4 c = p[(int64_t)k * H];
+#pragma unroll
+          for (int s = 0; s < S; ++s) {
+            const float x = xs[s][i], v = vs[s][i];
+            const float cn = rcp(1.0f + ex2(gxs[s][i] + c.x));
+            const float m = ffma(v, cn, 1.0f);
+            const float z = ffma(c.z, m, c.y * x);
+            const float th = ffma(rcp(1.0f + ex2(z)), -2.0f, 1.0f);
+            // d m / d x = -wc gs cn (1 - u) ((1 - cn) + u)
+            const float dm = -(v * gs) * (cn * ((1.0f - cn) + us[s][i]));
+            d[s] = ffma(c.w * ffma(-th, th, 1.0f), ffma(c.z, dm, c.y), d[s]);
+          }
+        }
+      }
+#pragma unroll
+      for (int s = 0; s < S; ++s) {
+        const float r = wave_sum(d[s] * gp[s]);
+        if (lane == 0) gout[s][i] = r * (0.5f / FETODE_LOG2E);   // c.y, c.z carry 2 log2e
+      }
+    }
+    __syncthreads();
+    if (own) {
+#pragma unroll
+      for (int s = 0; s < S; ++s) {
+        const float g = gout[s][lane];
+        ay[s] += g;
+        if (st == 3) {         // input y + dt ((k1 - k2) + k3)
+          ak1[s] += dt * g;
+          ak2[s] -= dt * g;
+          ak3[s] += dt * g;
+        } else if (st == 2) {  // input y + dt (k2 - k1 / 3)
+          ak2[s] += dt * g;
+          ak1[s] -= (dt * kThird) * g;
+        } else if (st == 1) {  // input y + (dt k1) / 3
+          ak1[s] += (dt * kThird) * g;
+        } else {               // input y: the step is done
+          const int64_t b = b0 + s;
+          lam[s] = ay[s] + (b < B ? a.grad_sol[((int64_t)step * B + b) * H + lane] : 0.f);
+        }
+      }
+    }
+  }
+  if (own) {
+#pragma unroll
+    for (int s = 0; s < S; ++s)
+      if (b0 + s < B) a.grad_h0[(b0 + s) * H + lane] = lam[s];
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// host
+// ---------------------------------------------------------------------------------------------
+int g_spw = 0;  // forced samples per workgroup (0: by batch size)
+
+bool drv_shape_ok(const fetode_ferro_t* fl) {
+  if (!fl || fl->branch_sign) return false;
+  const int D = fl->in_dim - fl->out_dim;
+  return fl->out_dim >= 1 && fl->out_dim <= kDrvHMax && D >= 1 && D <= kDrvDMax && fl->num_basis >= 1 &&
+         fl->num_basis <= kDrvKMax;
+}
+
+// Measured (profiles/driven_spw_sweep.log, forward at H = 64, K = 10, T = 96): a workgroup's time grows
+// in proportion to its samples, so sharing a parameter read pays only once every CU holds two
+// workgroups: one sample per workgroup up to B = 512, two up to 1024, four beyond.
+int choose_spw(int64_t B) {
+  if (g_spw) return g_spw;
+  return B <= 512 ? 1 : (B <= 1024 ? 2 : 4);
+}
+
+template <int S, bool TAPE>
+void launch_fixed_s(int K, int64_t grid, hipStream_t st, const DrivenArgs& a) {
+  const dim3 g((unsigned)grid), t(kDrvThreads);
+  if (K == 10) hipLaunchKernelGGL((driven_fixed_kernel<S, 10, TAPE>), g, t, 0, st, a);
+  else if (K == 12) hipLaunchKernelGGL((driven_fixed_kernel<S, 12, TAPE>), g, t, 0, st, a);
+  else hipLaunchKernelGGL((driven_fixed_kernel<S, 0, TAPE>), g, t, 0, st, a);
+}
+template <bool TAPE>
+void launch_fixed(int spw, int K, int64_t grid, hipStream_t st, const DrivenArgs& a) {
+  if (spw == 1) launch_fixed_s<1, TAPE>(K, grid, st, a);
+  else if (spw == 2) launch_fixed_s<2, TAPE>(K, grid, st, a);
+  else launch_fixed_s<4, TAPE>(K, grid, st, a);
+}
+
+template <int S>
+void launch_adj_s(int K, int64_t grid, hipStream_t st, const DrivenAdjArgs& a) {
+  const dim3 g((unsigned)grid), t(kDrvThreads);
+  if (K == 10) hipLaunchKernelGGL((driven_adj_kernel<S, 10>), g, t, 0, st, a);
+  else if (K == 12) hipLaunchKernelGGL((driven_adj_kernel<S, 12>), g, t, 0, st, a);
+  else hipLaunchKernelGGL((driven_adj_kernel<S, 0>), g, t, 0, st, a);
+}
+void launch_adj(int spw, int K, int64_t grid, hipStream_t st, const DrivenAdjArgs& a) {
+  if (spw == 1) launch_adj_s<1>(K, grid, st, a);
+  else if (spw == 2) launch_adj_s<2>(K, grid, st, a);
+  else launch_adj_s<4>(K, grid, st, a);
+}
+
+int driven_fixed(const fetode_ferro_t* fl, const void* plan, int32_t method, const float* h0, int64_t B, const float* u,
+                 int64_t n_eval, int64_t eval0, const float* dt, int32_t n_steps, const float* prev0, float* sol,
+                 float* prev_out, float* tape_hx, float* tape_phi, bool tape, void* stream) {
+  if (!drv_shape_ok(fl)) return set_err(FETODE_EUNSUPPORTED, "driven: shape outside the admitted family");
+  if (method != FETODE_RK4) return set_err(FETODE_EUNSUPPORTED, "driven: only rk4 (3/8 rule) is fused");
+  if (B < 0 || n_steps < 0 || eval0 < 0 || eval0 + 4 * (int64_t)n_steps > n_eval)
+    return set_err(FETODE_EINVAL, "driven: evaluations %lld + 4 * %d exceed the table's %lld rows", (long long)eval0,
+                   n_steps, (long long)n_eval);
+  if (B == 0 || n_steps == 0) return FETODE_OK;
+  if (!plan || !h0 || !u || !dt || !sol || (tape && (!tape_hx || !tape_phi)))
+    return set_err(FETODE_EINVAL, "driven: null pointer");
+  const int spw = choose_spw(B);
+  const int64_t grid = (B + spw - 1) / spw;
+  if (grid > 0x7fffffff) return set_err(FETODE_EUNSUPPORTED, "driven: batch too large");
+  DrivenArgs a{};
+  a.plan = (const float*)plan;
+  a.h0 = h0; a.u = u; a.dt = dt; a.prev0 = prev0; a.sol = sol; a.prev_out = prev_out;
+  a.tape_hx = tape_hx; a.tape_phi = tape_phi;
+  a.B = B; a.eval0 = eval0;
+  a.H = fl->out_dim; a.D = fl->in_dim - fl->out_dim; a.K = fl->num_basis; a.n_steps = n_steps;
+  a.gs = (float)fl->gate_slope; a.gsl2e = (float)fl->gate_slope * FETODE_LOG2E;
+  a.wc = (float)(-2.0 * (1.0 - fl->alpha));
+  if (tape) launch_fixed<true>(spw, a.K, grid, (hipStream_t)stream, a);
+  else launch_fixed<false>(spw, a.K, grid, (hipStream_t)stream, a);
+  LAUNCH_CHECK();
+  return FETODE_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fetode_driven_supported(const fetode_ferro_t* basis) { return drv_shape_ok(basis) ? 1 : 0; }
+
+int fetode_driven_set_spw(int spw) {
+  const int prev = g_spw;
+  if (spw == 0 || spw == 1 || spw == 2 || spw == 4) g_spw = spw;
+  return prev;
+}
+
+int64_t fetode_driven_plan_bytes(const fetode_ferro_t* basis) {
+  if (!drv_shape_ok(basis)) {
+    set_err(FETODE_EUNSUPPORTED, "driven: shape outside the admitted family");
+    return -1;
+  }
+  return (int64_t)sizeof(float) * drv_plan_floats(basis->in_dim, basis->out_dim, basis->num_basis);
+}
+
+int fetode_driven_plan_build(const fetode_ferro_t* basis, const float* gain, const float* bias, void* plan,
+                             void* stream) {
+  if (!drv_shape_ok(basis)) return set_err(FETODE_EUNSUPPORTED, "driven: shape outside the admitted family");
+  if (!basis->k || !basis->Ec || !basis->Ps || !basis->bias || !basis->coef || !gain || !bias || !plan)
+    return set_err(FETODE_EINVAL, "driven plan: null pointer");
+  const int64_t ne = drv_plan_elems(basis->in_dim, basis->out_dim, basis->num_basis);
+  hipLaunchKernelGGL(driven_plan_kernel, dim3(nblk(ne, 256)), dim3(256), 0, (hipStream_t)stream, *basis, gain, bias,
+                     (float*)plan);
+  LAUNCH_CHECK();
+  return FETODE_OK;
+}
+
+int fetode_driven_table(const float* tq, int64_t n_eval, const float* t_grid, int32_t T, const float* x, int64_t B,
+                        int32_t D, float* u, void* stream) {
+  if (n_eval < 0 || B < 0 || T < 2 || D < 1) return set_err(FETODE_EINVAL, "driven table: bad sizes");
+  const int64_t n = n_eval * B * D;
+  if (n == 0) return FETODE_OK;
+  if (!tq || !t_grid || !x || !u) return set_err(FETODE_EINVAL, "driven table: null pointer");
+  const int64_t blocks = (n + 255) / 256;
+  hipLaunchKernelGGL(driven_table_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0,
+                     (hipStream_t)stream, tq, n_eval, t_grid, T, x, B, D, u);
+  LAUNCH_CHECK();
+  return FETODE_OK;
+}
+
+int fetode_driven_fixed(const fetode_ferro_t* basis, const void* plan, int32_t method, const float* h0, int64_t B,
+                        const float* u, int64_t n_eval, int64_t eval0, const float* dt, int32_t n_steps,
+                        const float* prev0, float* sol, float* prev_out, void* stream) {
+  return driven_fixed(basis, plan, method, h0, B, u, n_eval, eval0, dt, n_steps, prev0, sol, prev_out, nullptr,
+                      nullptr, false, stream);
+}
+
+int fetode_driven_fixed_tape(const fetode_ferro_t* basis, const void* plan, int32_t method, const float* h0, int64_t B,
+                             const float* u, int64_t n_eval, int64_t eval0, const float* dt, int32_t n_steps,
+                             const float* prev0, float* sol, float* prev_out, float* tape_hx, float* tape_phi,
+                             void* stream) {
+  return driven_fixed(basis, plan, method, h0, B, u, n_eval, eval0, dt, n_steps, prev0, sol, prev_out, tape_hx,
+                      tape_phi, true, stream);
+}
+
+int fetode_driven_fixed_backward(const fetode_ferro_t* basis, const void* plan, int32_t method, int64_t B,
+                                 const float* dt, int32_t n_steps, const float* prev0, const float* tape_hx,
+                                 const float* tape_phi, const float* grad_sol, float* adj, float* grad_h0,
+                                 void* stream) {
+  if (!drv_shape_ok(basis)) return set_err(FETODE_EUNSUPPORTED, "driven: shape outside the admitted family");
+  if (method != FETODE_RK4) return set_err(FETODE_EUNSUPPORTED, "driven: only rk4 (3/8 rule) is fused");
+  if (B < 0 || n_steps < 0) return set_err(FETODE_EINVAL, "driven backward: bad sizes");
+  if (B == 0) return FETODE_OK;
+  if (!plan || !dt || !tape_hx || !tape_phi || !grad_sol || !adj || !grad_h0)
+    return set_err(FETODE_EINVAL, "driven backward: null pointer");
+  const int spw = choose_spw(B);
+  const int64_t grid = (B + spw - 1) / spw;
+  if (grid > 0x7fffffff) return set_err(FETODE_EUNSUPPORTED, "driven: batch too large");
+  DrivenAdjArgs a{};
+  a.plan = (const float*)plan;
+  a.dt = dt; a.prev0 = prev0; a.tape_hx = tape_hx; a.tape_phi = tape_phi; a.grad_sol = grad_sol;
+  a.adj = adj; a.grad_h0 = grad_h0;
+  a.B = B;
+  a.H = basis->out_dim; a.D = basis->in_dim - basis->out_dim; a.K = basis->num_basis; a.n_steps = n_steps;
+  a.gs = (float)basis->gate_slope; a.gsl2e = (float)basis->gate_slope * FETODE_LOG2E;
+  a.wc = (float)(-2.0 * (1.0 - basis->alpha));
+  launch_adj(spw, a.K, grid, (hipStream_t)stream, a);
+  LAUNCH_CHECK();
+  return FETODE_OK;
+}
+
+}  // extern "C"

@@ -599,9 +599,16 @@ def odeint(func, y0, t, *, rtol=1e-7, atol=1e-9, method=None, options=None, even
     if method == "dopri5":
         from .dopri5 import dopri5_solve
         return dopri5_solve(func, y0, tc, tp, reversed_, rtol, atol, options)
-    sched = get_schedule(tp, options.pop("step_size", None), reversed_)
+    step_size = options.pop("step_size", None)
+    sched = get_schedule(tp, step_size, reversed_)
     code = FIXED_METHODS[method]
     out = _try_fused(func, y0, sched, code)
     if out is not None:
         return out
+    if getattr(func, "_fetode_driven", False):
+        # an input-driven field (ecg.InputDrivenKANODEFunc): its own one-launch solve, or per stage
+        from .ecg import driven_solve
+        out = driven_solve(func, y0, t, tc, step_size, reversed_, code)
+        if out is not None:
+            return out
     return _per_stage_fixed(func, y0, sched, method, tc.dtype, reversed_)

@@ -779,6 +779,52 @@ int fetode_logistic_basis_backward(const float* x, int64_t B, int32_t in, int32_
                                    const float* b, const float* g_phi, float* g_x, float* g_a, float* g_b,
                                    void* workspace, void* stream);
 
+/* ---- the input-driven Ferro field (ECG NODE-RNN encoder, compare_noise_ecg.py:848-946) ----------
+ *     dh/dt = tanh(basis(cat[h, x(t)])) * gain + bias,   basis: FerroelectricBasis (H + D -> H)
+ * solved over a whole batch in one launch; every sample carries its own driving signal x(t) and its
+ * own hysteresis input (the reference resets the state before each sample's solve).  Admitted
+ * family: out_dim = H in 1..64, in_dim - out_dim = D in 1..4, num_basis in 1..16, constant
+ * branch_sign (NULL), method FETODE_RK4 (the other methods: FETODE_EUNSUPPORTED), any number of
+ * steps.  fetode_driven_supported is a host-only query of that family (1 / 0). */
+int fetode_driven_supported(const fetode_ferro_t* basis);
+/* Samples per workgroup of the driven kernels: 0 = by batch size (1 up to B = 512, 2 up to 1024, 4
+ * beyond), or 1 / 2 / 4 forced; any other argument changes nothing (so a negative one is a query).
+ * Returns the previous value.  Process-wide tuning / test knob. */
+int fetode_driven_set_spw(int spw);
+/* The packed parameters (per element gate_slope*log2e*Ec, 2*log2e*k, 2*log2e*k*Ec, coef*Ps in
+ * lane order; per output sum bias*coef, gain, bias), built by one launch; -1 outside the family. */
+int64_t fetode_driven_plan_bytes(const fetode_ferro_t* basis);
+int fetode_driven_plan_build(const fetode_ferro_t* basis, const float* gain, const float* bias, void* plan,
+                             void* stream);
+/* The driving table u (n_eval, B, D): LinearInterp1D(t_grid (T), x[b] (T, D)) at the times tq
+ * (n_eval), the reference's fp32 expression (clamp, searchsorted left, clamp(1, T-1),
+ * w = (t - t0) / (t1 - t0 + 1e-12), (1 - w) x0 + w x1).  x is (B, T, D). */
+int fetode_driven_table(const float* tq, int64_t n_eval, const float* t_grid, int32_t T, const float* x, int64_t B,
+                        int32_t D, float* u, void* stream);
+/* n_steps rk4 (3/8 rule) steps from h0 (B, H): evaluation e of the launch reads row eval0 + e of u
+ * (eval0 + 4 n_steps <= n_eval is checked), step s uses dt[s], sol (n_steps, B, H) receives the
+ * state after every step.  prev0 (B, H + D, nullable = zeros, the reset state) is the hysteresis
+ * input before the first evaluation and prev_out (nullable) receives the last evaluation's input,
+ * so a solve can be cut into consecutive launches that reproduce the single launch bit for bit. */
+int fetode_driven_fixed(const fetode_ferro_t* basis, const void* plan, int32_t method, const float* h0, int64_t B,
+                        const float* u, int64_t n_eval, int64_t eval0, const float* dt, int32_t n_steps,
+                        const float* prev0, float* sol, float* prev_out, void* stream);
+/* The same solve, recording every evaluation's input row tape_hx (n_eval, B, H + D) and
+ * pre-activation tape_phi (n_eval, B, H) at row eval0 + e. */
+int fetode_driven_fixed_tape(const fetode_ferro_t* basis, const void* plan, int32_t method, const float* h0, int64_t B,
+                             const float* u, int64_t n_eval, int64_t eval0, const float* dt, int32_t n_steps,
+                             const float* prev0, float* sol, float* prev_out, float* tape_hx, float* tape_phi,
+                             void* stream);
+/* Reverse sweep of a taped solve that started at evaluation 0: grad_sol (n_steps + 1, B, H) is
+ * d loss / d every trajectory row (row 0 = h0); writes adj (4 n_steps, B, H) = d loss / d every
+ * evaluation's output and grad_h0 (B, H).  The gate reads prev detached.  Parameter gradients are
+ * not summed here: they are fetode_ferro_backward over the 4 n_steps * B taped rows with
+ * g = adj * gain * (1 - tanh^2(tape_phi)), and row reductions for gain and bias. */
+int fetode_driven_fixed_backward(const fetode_ferro_t* basis, const void* plan, int32_t method, int64_t B,
+                                 const float* dt, int32_t n_steps, const float* prev0, const float* tape_hx,
+                                 const float* tape_phi, const float* grad_sol, float* adj, float* grad_h0,
+                                 void* stream);
+
 #ifdef __cplusplus
 }
 #endif
