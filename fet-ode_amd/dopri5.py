@@ -1512,6 +1512,13 @@ def _needs_grad(func, y0) -> bool:
 
 
 def dopri5_solve(func, y0, tc, tp, reversed_, rtol, atol, options):
+    if getattr(func, "_fetode_driven", False):
+        # an input-driven field (ecg.InputDrivenKANODEFunc) solved for one row without gradients: the
+        # one-launch solve with that row's own controller; more rows share one error norm (below)
+        from .ecg import driven_dopri5_odeint
+        sol = driven_dopri5_odeint(func, y0, tc, reversed_, rtol, atol, options)
+        if sol is not None:
+            return sol
     if _RESIDENT:
         sol = _try_ecg_resident(func, y0, tp, reversed_, rtol, atol, options)
         if sol is None:

@@ -397,11 +397,18 @@ class KanFet_MLP_NODE(CacheFreeState, nn.Module):
 # autograd it is the taped launch + one reverse sweep (fetode_driven_fixed_tape / _backward), the
 # parameter gradients one fetode_ferro_backward over the taped rows.  Everything else (a subclass, a
 # hooked module, another interpolator, a step_size option, another grid or method, a shape outside
-# the kernel's family) is integrated stage by stage; solver="dopri5" keeps the reference's
-# per-sample loop (the adaptive controller's RMS norm spans the batch, so a batched adaptive solve is
-# not the reference's result): that is the slow path.
+# the kernel's family) is integrated stage by stage.
+# solver="dopri5" (the reference's own run: rtol 1e-2, atol 1e-3): the reference solves one sample at
+# a time, so each sample has its own error norm, step sequence and attempt log.  Without gradients
+# that is ONE launch for the whole batch too (fetode_driven_dopri5): a workgroup owns a sample and
+# runs that sample's step controller, so row b is the reference's solve of sample b.  A batch-wide
+# controller (odeint with B > 1 rows: the RMS norm spans the batch) is a different computation and
+# stays on the host-driven loop; so does everything under autograd (the per-sample _Dopri5Grad loop,
+# whose gradient runs through dt into x(t)): that is the slow path.
 
 _FUSED_DRIVEN = _lib.os.environ.get("FETODE_FUSED_DRIVEN", "1") != "0"
+_DRIVEN_DOPRI5 = _lib.os.environ.get("FETODE_DRIVEN_DOPRI5", "1") != "0"
+_DRIVEN_MAX_TRACE = 1024   # attempts logged per sample (the count itself is exact beyond it)
 
 
 def set_fused_driven(enabled: bool) -> bool:
@@ -409,6 +416,15 @@ def set_fused_driven(enabled: bool) -> bool:
     off) or stage by stage.  Returns the previous value."""
     global _FUSED_DRIVEN
     prev, _FUSED_DRIVEN = _FUSED_DRIVEN, bool(enabled)
+    return prev
+
+
+def set_resident_driven_dopri5(enabled: bool) -> bool:
+    """Solve input-driven fields under dopri5 without gradients in one launch with a step controller
+    per sample (default on; env FETODE_DRIVEN_DOPRI5=0 turns it off) or on the host-driven loop,
+    sample by sample.  Returns the previous value."""
+    global _DRIVEN_DOPRI5
+    prev, _DRIVEN_DOPRI5 = _DRIVEN_DOPRI5, bool(enabled)
     return prev
 
 
@@ -427,6 +443,8 @@ class LinearInterp1D:
         self.T = t_grid.numel()
 
     def __call__(self, t_query):
+        if isinstance(t_query, torch.Tensor) and t_query.device != self.t.device:
+            t_query = t_query.to(self.t.device)   # the host-driven dopri5 loop hands the time over as a CPU scalar
         t = torch.clamp(t_query, self.t[0], self.t[-1])
         i = torch.searchsorted(self.t, t).clamp(1, self.T - 1)
         t0, t1 = self.t[i - 1], self.t[i]
@@ -544,9 +562,16 @@ def driven_eligible(func, t, tc, step_size, reversed_, method_code) -> bool:
     hooks, with an exact LinearInterp1D and the constant branch sign, integrated with rk4 over the
     interpolator's own increasing fp32 grid (tc: the host copy of t) with no step_size option, its
     shape in the kernel's family."""
-    if not _FUSED_DRIVEN or not _plain_driven(func) or method_code != _lib.RK4:
+    if not _FUSED_DRIVEN or method_code != _lib.RK4 or step_size is not None:
         return False
-    if step_size is not None or reversed_:
+    return _driven_rules(func, t, tc, reversed_)
+
+
+def _driven_rules(func, t, tc, reversed_) -> bool:
+    """What the fixed-grid and the adaptive solve share: the exact classes without hooks, forward time,
+    the interpolator's own fp32 grid (t: the caller's tensor or None, tc: its host copy), the constant
+    branch sign, a shape in the kernels' family."""
+    if not _plain_driven(func) or reversed_:
         return False
     tg = func._interp.t
     if not (isinstance(func._interp.x, torch.Tensor) and isinstance(tg, torch.Tensor)):
@@ -686,10 +711,129 @@ def driven_solve(func, y0, t, tc, step_size, reversed_, method_code):
     return _driven_launch(func, plan, d, h0, u, grids[2], _driven_prev0(func, h0, u), grids[2].numel(), False)[0]
 
 
+def driven_dopri5_eligible(func, t, tc, reversed_, rtol, atol, options) -> bool:
+    """The recognition rules of the one-launch dopri5 solve that need no GPU: those of the fixed-grid
+    solve (an exact InputDrivenKANODEFunc without hooks, an exact LinearInterp1D, the constant branch
+    sign, forward time over the interpolator's own increasing fp32 grid, a shape in the kernel's
+    family), scalar tolerances and only the scalar step-control options."""
+    from .dopri5 import _RESIDENT_OPTS
+    if not _DRIVEN_DOPRI5 or set(options) - _RESIDENT_OPTS:
+        return False
+    if not all(isinstance(v, (int, float)) and not isinstance(v, bool) for v in (rtol, atol)):
+        return False
+    if tc.dim() != 1 or tc.numel() < 2 or not bool((tc[1:] > tc[:-1]).all()):
+        return False
+    return _driven_rules(func, t, tc, reversed_)
+
+
+class DrivenDopri5Solve:
+    """Per-sample record of a one-launch dopri5 solve: ``nfev``, ``n_attempts`` and ``status`` (lists
+    over the batch) from the status words the solve read back, ``attempts[b]`` = sample b's
+    (t0, dt, error ratio, accepted) log (its first _DRIVEN_MAX_TRACE attempts), read back from the
+    device when first asked for; ``solution`` is the (T, B, H) tensor the launch wrote (a failed sample's
+    rows after its last output are not written)."""
+
+    _MESSAGES = {1: "non-finite values in state `y`", 2: "underflow in dt", 3: "max_num_steps exceeded"}
+
+    def __init__(self, stats, att, solution):
+        self._att, self._host, self.solution = att, None, solution
+        self.nfev, self.n_attempts, self.status = (list(c) for c in zip(*stats.tolist()))
+
+    @property
+    def attempts(self):
+        if self._host is None:
+            n = [min(k, self._att.shape[1]) for k in self.n_attempts]
+            rows = self._att[:, :max(n)].tolist() if n and max(n) else [[]] * len(n)
+            self._host = [[(a[0], a[1], a[2], bool(a[3])) for a in r[:k]] for r, k in zip(rows, n)]
+        return self._host
+
+    def sample(self, b):
+        """Sample b's record in the shape of dopri5.ResidentSolve (scalars and one attempt list)."""
+        from types import SimpleNamespace
+        return SimpleNamespace(nfev=self.nfev[b], n_attempts=self.n_attempts[b], attempts=self.attempts[b])
+
+    def raise_for_status(self):
+        """torchdiffeq's assertion of the lowest failing sample, naming it."""
+        for b, s in enumerate(self.status):
+            if s:
+                raise AssertionError(f"{self._MESSAGES.get(s, 'solver status %d' % s)} (sample {b})")
+
+
+def driven_dopri5_solve(func, y0, tc, reversed_, rtol, atol, options, reset=False, evlog=None, t=None):
+    """The one-launch dopri5 solve of a recognised input-driven field with one step controller per
+    row of y0 (B, H): (solution (T, B, H), DrivenDopri5Solve), or None where the solve is not the
+    kernel's (not eligible, a tensor elsewhere or in another format, something requiring grad, step
+    options the kernel declines).  Row b is the solve of sample b alone.  The basis is left holding
+    every row's last evaluation input.  reset: the rows start from the reset hysteresis state (zeros)
+    instead of the stored one.  evlog: a (B, max_ev, 1 + D) fp32 tensor that receives every
+    evaluation's time and x(t) (tests).  The caller checks the record's status."""
+    from .dopri5 import _TABLEAU, _opts_array
+    if y0.dim() != 2 or y0.shape[0] < 1 or y0.dtype != torch.float32 or not y0.is_cuda:
+        return None
+    if not driven_dopri5_eligible(func, t, tc, reversed_, rtol, atol, options):
+        return None
+    x, tg = func._interp.x, func._interp.t
+    B, H = y0.shape
+    if x.dim() == 2:
+        x = x.unsqueeze(0).expand(B, -1, -1)
+    bas = func.basis
+    T, D, In = tg.numel(), bas.in_dim - bas.out_dim, bas.in_dim
+    if (x.dim() != 3 or tuple(x.shape) != (B, T, D) or H != bas.out_dim or x.dtype != torch.float32
+            or x.device != y0.device or tg.device != y0.device):
+        return None
+    params = _driven_tensors(func)
+    if any(p.device != y0.device or p.dtype != torch.float32 for p in params):
+        return None
+    if torch.is_grad_enabled() and (y0.requires_grad or x.requires_grad or any(p.requires_grad for p in params)):
+        return None
+    dev = y0.device
+    ent = _driven_plan(func, dev)
+    if ent is None:
+        return None
+    plan, d, _ = ent
+    h0, xc, tgc = _lib.f32c(y0), _lib.f32c(x), _lib.f32c(tg)
+    prev0 = None
+    if not reset:
+        prev0 = _driven_prev0(func, h0, driven_table(tgc, xc, tgc[:1]))
+    sol = torch.empty(T, B, H, device=dev, dtype=torch.float32)
+    prev_out = torch.empty(B, In, device=dev, dtype=torch.float32)
+    stats = torch.empty(B, 3, device=dev, dtype=torch.int32)
+    att = torch.empty(B, _DRIVEN_MAX_TRACE, 4, device=dev, dtype=torch.float64)
+    opts = _opts_array(options)
+    rc = _lib.load().fetode_driven_dopri5(
+        _lib.ctypes.byref(d), plan.data_ptr(), h0.data_ptr(), B, xc.data_ptr(), tgc.data_ptr(), T, float(rtol),
+        float(atol), opts.ctypes.data_as(_lib.ctypes.POINTER(_lib.ctypes.c_double)),
+        _TABLEAU.ctypes.data_as(_lib.ctypes.POINTER(_lib.ctypes.c_float)), _lib.ptr(prev0), sol.data_ptr(),
+        prev_out.data_ptr(), stats.data_ptr(), att.data_ptr(), _DRIVEN_MAX_TRACE, _lib.ptr(evlog),
+        0 if evlog is None else evlog.shape[1], _lib.stream_handle(dev))
+    if rc == _lib.FETODE_EUNSUPPORTED:   # declined before the launch: nothing was touched
+        return None
+    _lib.check(rc, "fetode_driven_dopri5")
+    bas._prev = prev_out   # prev_x <- the last evaluation's input (ferro_class.py:409), row by row
+    return sol, DrivenDopri5Solve(stats, att, sol)
+
+
+def driven_dopri5_odeint(func, y0, tc, reversed_, rtol, atol, options):
+    """dopri5_solve's hook: odeint(func, h0 (1, H), t_grid, method="dopri5") of a recognised field
+    without gradients.  One row only: with more rows odeint's error norm spans the batch, which is
+    not this kernel's computation."""
+    if y0.dim() != 2 or y0.shape[0] != 1:
+        return None
+    out = driven_dopri5_solve(func, y0, tc, reversed_, rtol, atol, options)
+    if out is None:
+        return None
+    sol, rec = out
+    from .dopri5 import dopri5_solve
+    dopri5_solve.last = rec.sample(0)
+    rec.raise_for_status()
+    return sol
+
+
 class OneODEEncoder(CacheFreeState, nn.Module):
     """compare_noise_ecg.py:910-946, for a whole batch: xb (B, T, D) -> h_traj (T, B, H) (or the last
     row (B, H)); row b is the reference's solve of sample b.  Afterwards the basis holds what the
-    reference is left with: the last sample's state."""
+    reference is left with: the last sample's state.  last_solve: the DrivenDopri5Solve of the last
+    forward when it was the one-launch dopri5 solve, else None."""
 
     def __init__(self, input_size, hidden_size, num_basis, solver="rk4", rtol=1e-3, atol=1e-4, return_traj=True):
         super().__init__()
@@ -700,6 +844,29 @@ class OneODEEncoder(CacheFreeState, nn.Module):
         self.return_traj = return_traj
         self.lift = nn.Linear(input_size, hidden_size)
         self.odefunc = InputDrivenKANODEFunc(input_size, hidden_size, num_basis)
+        self.last_solve = None
+
+    def _solve_dopri5(self, xb, t_grid):
+        """The whole batch under dopri5 in one launch, a step controller per sample, when nothing needs
+        a gradient and the solve is the kernel's; None otherwise (_solve then starts over: it sets the
+        interpolator and resets the state itself)."""
+        if not _DRIVEN_DOPRI5:
+            return None
+        if torch.is_grad_enabled() and (xb.requires_grad or any(p.requires_grad for p in self.parameters())):
+            return None
+        f = self.odefunc
+        if not hasattr(f.basis, "reset_state"):
+            return None
+        f.set_interpolator(LinearInterp1D(t_grid, xb if xb.size(0) > 1 else xb[0]))
+        f.basis.reset_state()   # every row starts from the reset state (the reference solves it alone)
+        out = driven_dopri5_solve(f, self.lift(xb[:, 0]), t_grid.detach().cpu(), False, self.rtol, self.atol, {},
+                                  reset=True, t=t_grid)
+        if out is None:
+            return None
+        h_traj, self.last_solve = out
+        f.basis._prev = f.basis._prev[-1:].clone()   # the last sample's last evaluation input
+        self.last_solve.raise_for_status()
+        return h_traj
 
     def _solve(self, xb, t_grid):
         basis = self.odefunc.basis
@@ -717,9 +884,12 @@ class OneODEEncoder(CacheFreeState, nn.Module):
         return_traj = self.return_traj if return_traj is None else return_traj
         B, T = xb.size(0), xb.size(1)
         t_grid = torch.linspace(0.0, 1.0, steps=T, device=xb.device, dtype=xb.dtype)
-        if self.solver == "dopri5" and B > 1:   # adaptive: the reference's per-sample loop (slow path)
+        self.last_solve = None
+        h_traj = self._solve_dopri5(xb, t_grid) if self.solver == "dopri5" else None
+        if h_traj is None and self.solver == "dopri5" and B > 1:
+            # under autograd (or declined): the reference's per-sample loop (slow path)
             h_traj = torch.cat([self._solve(xb[b:b + 1], t_grid) for b in range(B)], dim=1)
-        else:
+        elif h_traj is None:
             h_traj = self._solve(xb, t_grid)
             basis = self.odefunc.basis
             if basis._prev.shape[0] > 1:

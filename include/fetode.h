@@ -824,6 +824,26 @@ int fetode_driven_fixed_backward(const fetode_ferro_t* basis, const void* plan, 
                                  const float* dt, int32_t n_steps, const float* prev0, const float* tape_hx,
                                  const float* tape_phi, const float* grad_sol, float* adj, float* grad_h0,
                                  void* stream);
+/* The same field under torchdiffeq's dopri5 over the output times t_grid (T >= 2, fp32, increasing:
+ * the interpolator's own knots), the whole batch in one launch with one step controller PER SAMPLE:
+ * sample b's error norm runs over its own H elements, so it takes the steps the reference's solve of
+ * that sample alone takes (the reference solves one sample at a time).  x is (B, T, D); the kernel
+ * interpolates x(t) at every evaluation time itself.  opts[7] = first_step (<= 0: selected), safety,
+ * ifactor, dfactor, min_step, max_step, max_num_steps (counted per output interval); tableau = beta
+ * (6 x 6), c_err (7), c_mid (7) in fp32.  prev0 (B, H + D, nullable = zeros) as in
+ * fetode_driven_fixed.  Written per sample: sol (T, B, H) rows (row 0 = h0; a failed sample stops
+ * and leaves its later rows untouched), prev_out (B, H + D, nullable) the last evaluation's input,
+ * stats (B, 3) = nfev, attempts, status (0 ok, 1 non-finite state or error ratio, 2 underflow in
+ * dt, 3 max_num_steps exceeded), the attempt log (B, max_attempts, 4) = t0, dt, error ratio,
+ * accepted (the count stays exact beyond max_attempts) and, when evlog is not NULL, every
+ * evaluation's time and x(t) in evlog (B, max_ev, 1 + D) (a kernel instantiation of its own: a
+ * solve without it does not pay for it).  Any B (one workgroup per sample).  FETODE_EUNSUPPORTED:
+ * a shape outside fetode_driven_supported, or step options under which a rejected step need not
+ * shrink (min_step > 0, safety >= 1 or dfactor >= 1) without max_num_steps <= 2^20. */
+int fetode_driven_dopri5(const fetode_ferro_t* basis, const void* plan, const float* h0, int64_t B, const float* x,
+                         const float* t_grid, int32_t T, double rtol, double atol, const double* opts,
+                         const float* tableau, const float* prev0, float* sol, float* prev_out, int32_t* stats,
+                         double* attempts, int32_t max_attempts, float* evlog, int32_t max_ev, void* stream);
 
 #ifdef __cplusplus
 }
