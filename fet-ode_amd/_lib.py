@@ -313,6 +313,16 @@ SIGNATURES = {
                                             ctypes.c_int32, ctypes.c_double, ctypes.c_double,
                                             ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_float), _vp, _vp,
                                             _vp, _vp, _vp, ctypes.c_int32, _vp, ctypes.c_int32, _vp]),
+    "fetode_driven_dopri5_tape": (ctypes.c_int, [ctypes.POINTER(FerroDesc), _vp, _vp, ctypes.c_int64, _vp, _vp,
+                                                 ctypes.c_int32, ctypes.c_double, ctypes.c_double,
+                                                 ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_float), _vp,
+                                                 _vp, _vp, _vp, _vp, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp,
+                                                 ctypes.c_int32, _vp]),
+    "fetode_driven_dopri5_backward": (ctypes.c_int, [ctypes.POINTER(FerroDesc), _vp, ctypes.c_int64, _vp,
+                                                     ctypes.c_int32, ctypes.c_double, ctypes.c_double,
+                                                     ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_float),
+                                                     _vp, _vp, _vp, ctypes.c_int32, _vp, _vp, _vp, _vp, ctypes.c_int32,
+                                                     _vp, ctypes.c_int32, _vp, _vp, _vp]),
 }
 
 _lib: Optional[ctypes.CDLL] = None

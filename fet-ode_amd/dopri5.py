@@ -1513,8 +1513,9 @@ def _needs_grad(func, y0) -> bool:
 
 def dopri5_solve(func, y0, tc, tp, reversed_, rtol, atol, options):
     if getattr(func, "_fetode_driven", False):
-        # an input-driven field (ecg.InputDrivenKANODEFunc) solved for one row without gradients: the
-        # one-launch solve with that row's own controller; more rows share one error norm (below)
+        # an input-driven field (ecg.InputDrivenKANODEFunc) solved for one row: the one-launch solve with
+        # that row's own controller (without gradients; under autograd only with
+        # ecg.set_resident_driven_dopri5_training on); more rows share one error norm (below)
         from .ecg import driven_dopri5_odeint
         sol = driven_dopri5_odeint(func, y0, tc, reversed_, rtol, atol, options)
         if sol is not None:

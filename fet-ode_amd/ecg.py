@@ -27,6 +27,7 @@ FETODE_ECG_DOPRI5_TAPE=1) a No_MLP_KANODEFunc training solve is the device-resid
 """
 from __future__ import annotations
 
+from types import SimpleNamespace
 from typing import Optional
 
 import torch
@@ -403,12 +404,16 @@ class KanFet_MLP_NODE(CacheFreeState, nn.Module):
 # that is ONE launch for the whole batch too (fetode_driven_dopri5): a workgroup owns a sample and
 # runs that sample's step controller, so row b is the reference's solve of sample b.  A batch-wide
 # controller (odeint with B > 1 rows: the RMS norm spans the batch) is a different computation and
-# stays on the host-driven loop; so does everything under autograd (the per-sample _Dopri5Grad loop,
-# whose gradient runs through dt into x(t)): that is the slow path.
+# stays on the host-driven loop.  Under autograd the default is the per-sample _Dopri5Grad loop (the
+# slow path); with set_resident_driven_dopri5_training(True) it is the taped launch and one reverse
+# sweep (fetode_driven_dopri5_tape / _backward), whose gradient runs through dt into
+# x(t) like autograd's does — or, with step_grad=False, treats the step sequence as constants.
 
 _FUSED_DRIVEN = _lib.os.environ.get("FETODE_FUSED_DRIVEN", "1") != "0"
 _DRIVEN_DOPRI5 = _lib.os.environ.get("FETODE_DRIVEN_DOPRI5", "1") != "0"
 _DRIVEN_MAX_TRACE = 1024   # attempts logged per sample (the count itself is exact beyond it)
+_DRIVEN_DOPRI5_TRAIN = [_lib.os.environ.get("FETODE_DRIVEN_DOPRI5_TRAIN", "0") == "1", True]   # enabled, step_grad
+_DRIVEN_TAPE_ATTEMPTS = 64   # attempts per sample the first taped launch has room for
 
 
 def set_fused_driven(enabled: bool) -> bool:
@@ -425,6 +430,19 @@ def set_resident_driven_dopri5(enabled: bool) -> bool:
     sample by sample.  Returns the previous value."""
     global _DRIVEN_DOPRI5
     prev, _DRIVEN_DOPRI5 = _DRIVEN_DOPRI5, bool(enabled)
+    return prev
+
+
+def set_resident_driven_dopri5_training(enabled: bool, step_grad: bool = True):
+    """Train input-driven fields under dopri5 through the one-launch solve: a taped launch with a step
+    controller per sample, one reverse sweep, and the parameter sums over the taped rows (default
+    off; env FETODE_DRIVEN_DOPRI5_TRAIN=1 turns it on) instead of the per-sample _Dopri5Grad loop.
+    step_grad=True: the gradient autograd forms through torchdiffeq (error ratio, step-size control,
+    initial step, stage times into x(t)); False: the gradient of the discrete solve on the step
+    sequence the forward took (rejected attempts contribute nothing).  Returns the previous
+    (enabled, step_grad), which restores it: set_resident_driven_dopri5_training(*prev)."""
+    prev = tuple(_DRIVEN_DOPRI5_TRAIN)
+    _DRIVEN_DOPRI5_TRAIN[:] = [bool(enabled), bool(step_grad)]
     return prev
 
 
@@ -726,6 +744,30 @@ def driven_dopri5_eligible(func, t, tc, reversed_, rtol, atol, options) -> bool:
     return _driven_rules(func, t, tc, reversed_)
 
 
+def _driven_dopri5_inputs(func, y0, tc, reversed_, rtol, atol, options, t):
+    """What the untaped and the taped one-launch dopri5 solve ask of their inputs, stated once:
+    driven_dopri5_eligible, y0 (B >= 1, H) fp32 on a GPU, and the series, the grid and the parameters
+    fp32 on that GPU with matching shapes.  (x (B, T, D), the grid, the parameters) or None; who may
+    require grad is the caller's rule."""
+    if y0.dim() != 2 or y0.shape[0] < 1 or y0.dtype != torch.float32 or not y0.is_cuda:
+        return None
+    if not driven_dopri5_eligible(func, t, tc, reversed_, rtol, atol, options):
+        return None
+    x, tg = func._interp.x, func._interp.t
+    B, H = y0.shape
+    if x.dim() == 2:
+        x = x.unsqueeze(0).expand(B, -1, -1)
+    bas = func.basis
+    T, D = tg.numel(), bas.in_dim - bas.out_dim
+    if (x.dim() != 3 or tuple(x.shape) != (B, T, D) or H != bas.out_dim or x.dtype != torch.float32
+            or x.device != y0.device or tg.device != y0.device):
+        return None
+    params = _driven_tensors(func)
+    if any(p.device != y0.device or p.dtype != torch.float32 for p in params):
+        return None
+    return x, tg, params
+
+
 class DrivenDopri5Solve:
     """Per-sample record of a one-launch dopri5 solve: ``nfev``, ``n_attempts`` and ``status`` (lists
     over the batch) from the status words the solve read back, ``attempts[b]`` = sample b's
@@ -768,24 +810,14 @@ def driven_dopri5_solve(func, y0, tc, reversed_, rtol, atol, options, reset=Fals
     instead of the stored one.  evlog: a (B, max_ev, 1 + D) fp32 tensor that receives every
     evaluation's time and x(t) (tests).  The caller checks the record's status."""
     from .dopri5 import _TABLEAU, _opts_array
-    if y0.dim() != 2 or y0.shape[0] < 1 or y0.dtype != torch.float32 or not y0.is_cuda:
+    rec = _driven_dopri5_inputs(func, y0, tc, reversed_, rtol, atol, options, t)
+    if rec is None:
         return None
-    if not driven_dopri5_eligible(func, t, tc, reversed_, rtol, atol, options):
-        return None
-    x, tg = func._interp.x, func._interp.t
-    B, H = y0.shape
-    if x.dim() == 2:
-        x = x.unsqueeze(0).expand(B, -1, -1)
-    bas = func.basis
-    T, D, In = tg.numel(), bas.in_dim - bas.out_dim, bas.in_dim
-    if (x.dim() != 3 or tuple(x.shape) != (B, T, D) or H != bas.out_dim or x.dtype != torch.float32
-            or x.device != y0.device or tg.device != y0.device):
-        return None
-    params = _driven_tensors(func)
-    if any(p.device != y0.device or p.dtype != torch.float32 for p in params):
-        return None
+    x, tg, params = rec
     if torch.is_grad_enabled() and (y0.requires_grad or x.requires_grad or any(p.requires_grad for p in params)):
         return None
+    bas = func.basis
+    (B, H), T, In = y0.shape, tg.numel(), bas.in_dim
     dev = y0.device
     ent = _driven_plan(func, dev)
     if ent is None:
@@ -820,6 +852,8 @@ def driven_dopri5_odeint(func, y0, tc, reversed_, rtol, atol, options):
     if y0.dim() != 2 or y0.shape[0] != 1:
         return None
     out = driven_dopri5_solve(func, y0, tc, reversed_, rtol, atol, options)
+    if out is None:   # under autograd, with the training knob on: the taped solve (raises for a failed sample)
+        out = driven_dopri5_train(func, y0, tc, reversed_, rtol, atol, options)
     if out is None:
         return None
     sol, rec = out
@@ -827,6 +861,165 @@ def driven_dopri5_odeint(func, y0, tc, reversed_, rtol, atol, options):
     dopri5_solve.last = rec.sample(0)
     rec.raise_for_status()
     return sol
+
+
+def tape_attempts_needed(n_attempts, cap):
+    """The cap -> rerun decision of the taped solve: 0 when every sample's exact attempt count fits
+    the cap the launch had room for, else the room the rerun needs."""
+    most = max(n_attempts, default=0)
+    return most if most > cap else 0
+
+
+def tape_prev_rows(thx, prev0):
+    """prev of every taped row (B, n, In) for the parameter-sum pass: the preceding row of the same
+    sample; prev0 (B, In), or the reset state's zeros for None, before a sample's row 0."""
+    first = torch.zeros_like(thx[:, :1]) if prev0 is None else prev0.unsqueeze(1)
+    return torch.cat([first, thx[:, :-1]], dim=1)
+
+
+def _driven_dopri5_tape_launch(d, plan, h0, xc, tgc, rtol, atol, opts, prev0, max_att):
+    from .dopri5 import _TABLEAU
+    dev = h0.device
+    B, H = h0.shape
+    T, D = xc.shape[1], xc.shape[2]
+    In, max_ev = H + D, 2 + 6 * max_att
+    f32 = dict(device=dev, dtype=torch.float32)
+    sol = torch.empty(T, B, H, **f32)
+    prev_out = torch.empty(B, In, **f32)
+    stats = torch.empty(B, 3, device=dev, dtype=torch.int32)
+    att = torch.empty(B, max_att, 4, device=dev, dtype=torch.float64)
+    tape = SimpleNamespace(hx=torch.empty(B, max_ev, In, **f32), phi=torch.empty(B, max_ev, H, **f32),
+                           t=torch.empty(B, max_ev, **f32), slope=torch.empty(B, max_ev, D, **f32),
+                           init=torch.empty(B, 5, device=dev, dtype=torch.float64), max_ev=max_ev, max_att=max_att)
+    rc = _lib.load().fetode_driven_dopri5_tape(
+        _lib.ctypes.byref(d), plan.data_ptr(), h0.data_ptr(), B, xc.data_ptr(), tgc.data_ptr(), T, float(rtol),
+        float(atol), opts.ctypes.data_as(_lib.ctypes.POINTER(_lib.ctypes.c_double)),
+        _TABLEAU.ctypes.data_as(_lib.ctypes.POINTER(_lib.ctypes.c_float)), _lib.ptr(prev0), sol.data_ptr(),
+        prev_out.data_ptr(), stats.data_ptr(), att.data_ptr(), max_att, tape.hx.data_ptr(), tape.phi.data_ptr(),
+        tape.t.data_ptr(), tape.slope.data_ptr(), tape.init.data_ptr(), max_ev, _lib.stream_handle(dev))
+    if rc == _lib.FETODE_EUNSUPPORTED:   # declined before the launch: nothing was touched
+        return None
+    _lib.check(rc, "fetode_driven_dopri5_tape")
+    return sol, prev_out, stats, att, tape
+
+
+def driven_dopri5_taped_solve(func, plan, d, h0, xc, tgc, rtol, atol, options, prev0, cap=None):
+    """The taped one-launch solve with room for `cap` attempts per sample (default
+    _DRIVEN_TAPE_ATTEMPTS); where a sample's exact attempt count exceeds it, the solve is run again
+    from the same state with room for all (deterministic: the same bits).  (solution, record, tape),
+    or None where the kernel declines the step options.  Leaves the basis with every row's last
+    evaluation input."""
+    from .dopri5 import _opts_array
+    opts = _opts_array(options)
+    cap = _DRIVEN_TAPE_ATTEMPTS if cap is None else max(1, int(cap))
+    out = _driven_dopri5_tape_launch(d, plan, h0, xc, tgc, rtol, atol, opts, prev0, cap)
+    if out is None:
+        return None
+    rec = DrivenDopri5Solve(out[2], out[3], out[0])
+    more = tape_attempts_needed(rec.n_attempts, cap)
+    if more:
+        out = _driven_dopri5_tape_launch(d, plan, h0, xc, tgc, rtol, atol, opts, prev0, more)
+        rec = DrivenDopri5Solve(out[2], out[3], out[0])
+    sol, prev_out, stats, att, tape = out
+    tape.stats, tape.att, tape.opts = stats, att, opts
+    func.basis._prev = prev_out   # prev_x <- the last evaluation's input (ferro_class.py:409), row by row
+    return sol, rec, tape
+
+
+class _TapeDeclined(Exception):
+    """fetode_driven_dopri5_tape declined the step options before launching (nothing was touched)."""
+
+
+class _DrivenDopri5Fn(torch.autograd.Function):
+    """Taped one-launch dopri5 solve with a step controller per sample; backward = one reverse sweep
+    (adjoints of every evaluation's output and of h0, through the step control unless step_grad is
+    off), then the parameter sums over the taped rows as in _DrivenFn.  reset: the rows start from the
+    reset hysteresis state.  A failing sample raises in forward; the record of the last forward is
+    _DrivenDopri5Fn.last, the adj (B, max_ev, H) of the last backward _DrivenDopri5Fn.last_adj."""
+
+    last = None
+    last_adj = None
+
+    @staticmethod
+    def forward(ctx, f, x, t_grid, h0, rtol, atol, opts, reset, *params):
+        dev = h0.device
+        plan, d, keep = _driven_plan(f, dev)
+        h0c, xc, tgc = _lib.f32c(h0.detach()), _lib.f32c(x), _lib.f32c(t_grid.detach())
+        prev0 = None if reset else _driven_prev0(f, h0c, driven_table(tgc, xc, tgc[:1]))
+        out = driven_dopri5_taped_solve(f, plan, d, h0c, xc, tgc, rtol, atol, opts, prev0)
+        if out is None:
+            raise _TapeDeclined()
+        sol, rec, tape = out
+        _DrivenDopri5Fn.last = rec
+        rec.raise_for_status()
+        ctx.f, ctx.plan, ctx.d, ctx.keep, ctx.tape, ctx.rec = f, plan, d, keep, tape, rec
+        ctx.tg, ctx.prev0, ctx.tols = tgc, prev0, (float(rtol), float(atol))
+        ctx.step_grad = bool(_DRIVEN_DOPRI5_TRAIN[1])
+        ctx.save_for_backward(*[p.detach() for p in params])
+        return sol
+
+    @staticmethod
+    def backward(ctx, grad):
+        from .dopri5 import _TABLEAU
+        params = ctx.saved_tensors
+        f, tape, dev = ctx.f, ctx.tape, grad.device
+        g = _lib.f32c(grad)
+        T, B, H = g.shape
+        adj = torch.empty_like(tape.phi)
+        gh0 = torch.empty(B, H, device=dev, dtype=torch.float32)
+        _lib.check(_lib.load().fetode_driven_dopri5_backward(
+            _lib.ctypes.byref(ctx.d), ctx.plan.data_ptr(), B, ctx.tg.data_ptr(), T, ctx.tols[0], ctx.tols[1],
+            tape.opts.ctypes.data_as(_lib.ctypes.POINTER(_lib.ctypes.c_double)),
+            _TABLEAU.ctypes.data_as(_lib.ctypes.POINTER(_lib.ctypes.c_float)), _lib.ptr(ctx.prev0),
+            tape.stats.data_ptr(), tape.att.data_ptr(), tape.max_att, tape.hx.data_ptr(), tape.phi.data_ptr(),
+            tape.slope.data_ptr(), tape.init.data_ptr(), tape.max_ev, g.data_ptr(), int(ctx.step_grad),
+            adj.data_ptr(), gh0.data_ptr(), _lib.stream_handle(dev)), "fetode_driven_dopri5_backward")
+        _DrivenDopri5Fn.last_adj = adj   # every evaluation's output adjoint (tests and tooling)
+        want = ctx.needs_input_grad[8:]
+        grads = [None] * 7
+        if any(want):
+            # rows at or beyond a sample's nfev are zeros in the tape and in adj, so the sums may run over
+            # the rows up to the batch's longest solve
+            ne = max(ctx.rec.nfev)
+            thx, tphi, adj = tape.hx[:, :ne], tape.phi[:, :ne], adj[:, :ne]
+            gain = params[5]
+            y = torch.tanh(tphi)
+            if any(want[:5]):
+                from .autograd_ops import _ferro_backward_generic
+                In = thx.shape[2]
+                gphi = (adj * gain) * (1.0 - y * y)
+                prev = tape_prev_rows(thx, ctx.prev0)
+                _, fg = _ferro_backward_generic(f.basis, thx.reshape(B * ne, In), prev.reshape(B * ne, In), False, None,
+                                                gphi.reshape(B * ne, H), False, list(want[:5]))
+                grads[:5] = fg
+            if want[5]:
+                grads[5] = (adj * y).sum(dim=(0, 1))
+            if want[6]:
+                grads[6] = adj.sum(dim=(0, 1))
+        return (None, None, None, gh0 if ctx.needs_input_grad[3] else None, None, None, None, None, *grads)
+
+
+def driven_dopri5_train(func, y0, tc, reversed_, rtol, atol, options, reset=False, t=None):
+    """The taped one-launch dopri5 solve under autograd, when set_resident_driven_dopri5_training is on:
+    (solution (T, B, H) with a grad_fn, DrivenDopri5Solve), or None where the solve is not the
+    kernel's (driven_dopri5_solve's rules), nothing requires grad, or the driving series does (the
+    sweep carries no adjoint to x).  One step controller per row of y0, as in driven_dopri5_solve.
+    A failing sample raises torchdiffeq's assertion, naming it."""
+    if not _DRIVEN_DOPRI5_TRAIN[0] or not torch.is_grad_enabled():
+        return None
+    rec = _driven_dopri5_inputs(func, y0, tc, reversed_, rtol, atol, options, t)
+    if rec is None:
+        return None
+    x, tg, params = rec
+    if x.requires_grad or not (y0.requires_grad or any(p.requires_grad for p in params)):
+        return None
+    if _driven_plan(func, y0.device) is None:
+        return None
+    try:
+        sol = _DrivenDopri5Fn.apply(func, x.detach(), tg, y0, rtol, atol, dict(options), bool(reset), *params)
+    except _TapeDeclined:
+        return None
+    return sol, _DrivenDopri5Fn.last
 
 
 class OneODEEncoder(CacheFreeState, nn.Module):
@@ -847,20 +1040,27 @@ class OneODEEncoder(CacheFreeState, nn.Module):
         self.last_solve = None
 
     def _solve_dopri5(self, xb, t_grid):
-        """The whole batch under dopri5 in one launch, a step controller per sample, when nothing needs
-        a gradient and the solve is the kernel's; None otherwise (_solve then starts over: it sets the
+        """The whole batch under dopri5 in one launch, a step controller per sample, when the solve is the
+        kernel's and nothing needs a gradient — or, with set_resident_driven_dopri5_training on, the
+        parameters or lift do (the taped launch, B >= 1) but the series does not; None otherwise (_solve then starts over: it sets the
         interpolator and resets the state itself)."""
         if not _DRIVEN_DOPRI5:
             return None
-        if torch.is_grad_enabled() and (xb.requires_grad or any(p.requires_grad for p in self.parameters())):
+        train = torch.is_grad_enabled() and (xb.requires_grad or any(p.requires_grad for p in self.parameters()))
+        if train and (xb.requires_grad or not _DRIVEN_DOPRI5_TRAIN[0]):
             return None
         f = self.odefunc
         if not hasattr(f.basis, "reset_state"):
             return None
         f.set_interpolator(LinearInterp1D(t_grid, xb if xb.size(0) > 1 else xb[0]))
         f.basis.reset_state()   # every row starts from the reset state (the reference solves it alone)
-        out = driven_dopri5_solve(f, self.lift(xb[:, 0]), t_grid.detach().cpu(), False, self.rtol, self.atol, {},
-                                  reset=True, t=t_grid)
+        solve = driven_dopri5_train if train else driven_dopri5_solve
+        try:
+            out = solve(f, self.lift(xb[:, 0]), t_grid.detach().cpu(), False, self.rtol, self.atol, {}, reset=True,
+                        t=t_grid)
+        except AssertionError:   # a failed sample of the taped solve: its record stays readable
+            self.last_solve = _DrivenDopri5Fn.last
+            raise
         if out is None:
             return None
         h_traj, self.last_solve = out

@@ -844,6 +844,39 @@ int fetode_driven_dopri5(const fetode_ferro_t* basis, const void* plan, const fl
                          const float* t_grid, int32_t T, double rtol, double atol, const double* opts,
                          const float* tableau, const float* prev0, float* sol, float* prev_out, int32_t* stats,
                          double* attempts, int32_t max_attempts, float* evlog, int32_t max_ev, void* stream);
+/* The same solve with a training tape (a kernel instantiation of its own; sol, prev_out, stats and the
+ * attempt log are bitwise fetode_driven_dopri5's).  Per sample and evaluation, in call order (f0, the
+ * initial-step probe unless first_step is given, then six evaluations per attempt, rejected ones
+ * included), row e < nfev of: tape_hx (B, max_ev, H + D) the input row, tape_phi (B, max_ev, H) the
+ * pre-activation, tape_t (B, max_ev) the evaluation time, tape_slope (B, max_ev, D) the slope
+ * (x1 - x0) / (t1 - t0 + 1e-12) of the series interval the interpolation used, 0 where the query lay
+ * strictly outside the grid (the clamp cut it).  Rows at or beyond nfev are zeroed; rows beyond
+ * max_ev are not recorded (stats stays exact: a caller that reads nfev > max_ev runs the solve again
+ * with room, and gets the same bits).  init_rec (B, 5) = d0, d1, d2, h0, h1 of the initial-step
+ * selection (zeros with first_step).  attempts must not be NULL. */
+int fetode_driven_dopri5_tape(const fetode_ferro_t* basis, const void* plan, const float* h0, int64_t B, const float* x,
+                              const float* t_grid, int32_t T, double rtol, double atol, const double* opts,
+                              const float* tableau, const float* prev0, float* sol, float* prev_out, int32_t* stats,
+                              double* attempts, int32_t max_attempts, float* tape_hx, float* tape_phi, float* tape_t,
+                              float* tape_slope, double* init_rec, int32_t max_ev, void* stream);
+/* Reverse sweep of a taped solve, one workgroup per sample walking that sample's attempts backwards
+ * from its own stats: grad_sol (T, B, H) is d loss / d solution; writes adj (B, max_ev, H) = d loss /
+ * d every evaluation's output (rows at or beyond nfev: zeros) and grad_h0 (B, H).  step_grad != 0: the
+ * gradient of the adaptive solve as autograd through torchdiffeq forms it (error ratio, step-size
+ * control, initial-step selection, and the evaluation times' adjoint through the slope of x(t));
+ * step_grad == 0: the gradient of the discrete solve on the step sequence the forward took (every dt,
+ * t0 and stage time a constant; the evaluations of rejected attempts get exact zeros).  The gate
+ * reads prev detached; x carries no adjoint.  A sample whose status is not 0, or whose attempts or
+ * evaluations exceed max_attempts / max_ev, gets zeros.  Parameter gradients are not summed here:
+ * they are fetode_ferro_backward over the B * max_ev taped rows (prev = the preceding row of the
+ * same sample, prev0 for its row 0) with g = adj * gain * (1 - tanh^2(tape_phi)), and row reductions
+ * for gain and bias.  opts, tableau, prev0 as given to the forward. */
+int fetode_driven_dopri5_backward(const fetode_ferro_t* basis, const void* plan, int64_t B, const float* t_grid,
+                                  int32_t T, double rtol, double atol, const double* opts, const float* tableau,
+                                  const float* prev0, const int32_t* stats, const double* attempts,
+                                  int32_t max_attempts, const float* tape_hx, const float* tape_phi,
+                                  const float* tape_slope, const double* init_rec, int32_t max_ev,
+                                  const float* grad_sol, int32_t step_grad, float* adj, float* grad_h0, void* stream);
 
 #ifdef __cplusplus
 }
