@@ -323,6 +323,12 @@ SIGNATURES = {
                                                      ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_float),
                                                      _vp, _vp, _vp, ctypes.c_int32, _vp, _vp, _vp, _vp, ctypes.c_int32,
                                                      _vp, ctypes.c_int32, _vp, _vp, _vp]),
+    "fetode_driven_param_grad_workspace": (ctypes.c_int64, [ctypes.POINTER(FerroDesc), ctypes.c_int64,
+                                                            ctypes.c_int64]),
+    "fetode_driven_param_grad": (ctypes.c_int, [ctypes.POINTER(FerroDesc), _vp, ctypes.c_int64, ctypes.c_int64,
+                                                ctypes.c_int64, ctypes.c_int64, _vp, ctypes.c_int64, _vp, _vp, _vp,
+                                                _vp, ctypes.POINTER(FerroGrad), _vp, _vp, _vp, _vp]),
+    "fetode_driven_param_grad_set_splits": (ctypes.c_int, [ctypes.c_int]),
 }
 
 _lib: Optional[ctypes.CDLL] = None

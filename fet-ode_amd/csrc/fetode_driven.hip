@@ -4,7 +4,8 @@
 //   driven_table_kernel   x(t) at every evaluation time, the reference's fp32 expression (:861-872)
 //   driven_plan_kernel    per-element constants + sum bias*coef per output, one launch
 //   driven_fixed_kernel   the whole fixed-grid solve; a workgroup owns its samples from h0 to the end
-//   driven_adj_kernel     the reverse sweep along the chain of evaluations (d/dh only)
+//   driven_adj_kernel     the reverse sweep along the chain of evaluations (d/dh only; the parameter
+//                         sums over the taped rows: fetode_driven_pgrad.hip or the generic Ferro backward)
 // The reference resets the hysteresis state before every sample's solve, so the samples are
 // independent: sample b carries its own driving row and its own prev.  branch_sign stays 1, so
 //     m = 1 - 2(1-alpha)(1-u) sigma(gs(-x-Ec)),   u = sigma(gs(x - prev))       (DESIGN §3 "Algebra").

@@ -19,7 +19,8 @@
 // step_grad = 0 freezes the step sequence: every dt, t0 and stage time is a constant, so there is no
 // control chain and no time adjoint, and a rejected attempt contributes exactly nothing.
 // Written: adj (B, max_ev, H) = d loss / d every evaluation's output (rows at or beyond nfev: zeros) and
-// grad_h0 (B, H).  The parameter sums are formed from adj and the tape by the caller.
+// grad_h0 (B, H).  The parameter sums are formed from adj and the tape by the caller
+// (fetode_driven_param_grad, fetode_driven_pgrad.hip, or the generic Ferro backward).
 #include <string.h>
 
 #include "fetode_common.h"

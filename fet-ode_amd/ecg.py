@@ -408,12 +408,16 @@ class KanFet_MLP_NODE(CacheFreeState, nn.Module):
 # slow path); with set_resident_driven_dopri5_training(True) it is the taped launch and one reverse
 # sweep (fetode_driven_dopri5_tape / _backward), whose gradient runs through dt into
 # x(t) like autograd's does — or, with step_grad=False, treats the step sequence as constants.
+# Both taped backwards form the parameter gradients from the sweep's adj: by default with the generic
+# Ferro backward over every taped row and two torch reductions, with set_fused_driven_param_grads(True)
+# in one driven-field kernel over the live rows (fetode_driven_param_grad).
 
 _FUSED_DRIVEN = _lib.os.environ.get("FETODE_FUSED_DRIVEN", "1") != "0"
 _DRIVEN_DOPRI5 = _lib.os.environ.get("FETODE_DRIVEN_DOPRI5", "1") != "0"
 _DRIVEN_MAX_TRACE = 1024   # attempts logged per sample (the count itself is exact beyond it)
 _DRIVEN_DOPRI5_TRAIN = [_lib.os.environ.get("FETODE_DRIVEN_DOPRI5_TRAIN", "0") == "1", True]   # enabled, step_grad
 _DRIVEN_TAPE_ATTEMPTS = 64   # attempts per sample the first taped launch has room for
+_DRIVEN_PARAM_GRADS = [_lib.os.environ.get("FETODE_DRIVEN_PARAM_GRADS", "0") == "1"]
 
 
 def set_fused_driven(enabled: bool) -> bool:
@@ -444,6 +448,20 @@ def set_resident_driven_dopri5_training(enabled: bool, step_grad: bool = True):
     prev = tuple(_DRIVEN_DOPRI5_TRAIN)
     _DRIVEN_DOPRI5_TRAIN[:] = [bool(enabled), bool(step_grad)]
     return prev
+
+
+def set_fused_driven_param_grads(enabled: bool) -> bool:
+    """Sum the parameter gradients of the taped driven solves (rk4 and dopri5) in one driven-field
+    kernel over the live taped rows (fetode_driven_param_grad) instead of the generic
+    Ferro backward over every taped row plus two torch reductions (default off; env
+    FETODE_DRIVEN_PARAM_GRADS=1 turns it on).  Returns the previous value."""
+    prev, _DRIVEN_PARAM_GRADS[0] = _DRIVEN_PARAM_GRADS[0], bool(enabled)
+    return prev
+
+
+def set_driven_param_grad_splits(s: int) -> int:
+    """fetode_driven_param_grad_set_splits: 0 = from the shape, 1..64 forced; returns the previous value."""
+    return int(_lib.load().fetode_driven_param_grad_set_splits(int(s)))
 
 
 def set_driven_samples_per_workgroup(spw: int) -> int:
@@ -657,6 +675,45 @@ def _driven_launch(f, plan, d, h0, u, dtv, prev0, n_steps, tape):
     return sol, thx, tphi
 
 
+def _driven_param_sums_generic(f, gain, want, thx, tphi, adj, prev_rows):
+    """The seven parameter gradients over every taped row (two leading dimensions, either order) by the
+    generic Ferro backward and two torch reductions; prev_rows() builds the rows' hysteresis inputs."""
+    grads = [None] * 7
+    H, In = tphi.shape[-1], thx.shape[-1]
+    y = torch.tanh(tphi)
+    if any(want[:5]):
+        from .autograd_ops import _ferro_backward_generic
+        gphi = (adj * gain) * (1.0 - y * y)
+        _, fg = _ferro_backward_generic(f.basis, thx.reshape(-1, In), prev_rows().reshape(-1, In), False, None,
+                                        gphi.reshape(-1, H), False, list(want[:5]))
+        grads[:5] = fg
+    if want[5]:
+        grads[5] = (adj * y).sum(dim=(0, 1))
+    if want[6]:
+        grads[6] = adj.sum(dim=(0, 1))
+    return grads
+
+
+def driven_param_grads(d, params, want, B, n_ev, stride_b, stride_e, nfev, nfev_stride, prev0, thx, tphi, adj):
+    """The seven parameter gradients (k, Ec, Ps, bias, coef, gain, bias; None where want is false) of
+    a taped driven solve in one call of fetode_driven_param_grad: d the basis descriptor, params the
+    seven tensors, row (b, e) of thx / tphi / adj at row b * stride_b + e * stride_e, nfev (int32,
+    nullable) sample b's live rows at nfev[b * nfev_stride], prev0 (B, In) or None (zeros)."""
+    lib = _lib.load()
+    dev = adj.device
+    out = [torch.empty(p.shape, device=dev, dtype=torch.float32) if w else None for p, w in zip(params, want)]
+    nb = lib.fetode_driven_param_grad_workspace(_lib.ctypes.byref(d), B, n_ev)
+    if nb < 0:
+        _lib.check(_lib.FETODE_EUNSUPPORTED, "fetode_driven_param_grad_workspace")
+    ws = torch.empty(max(1, nb // 4), device=dev, dtype=torch.float32)
+    gs = _lib.FerroGrad(*[_lib.ptr(t) for t in out[:5]])
+    _lib.check(lib.fetode_driven_param_grad(
+        _lib.ctypes.byref(d), params[5].data_ptr(), B, n_ev, stride_b, stride_e, _lib.ptr(nfev), nfev_stride,
+        _lib.ptr(prev0), thx.data_ptr(), tphi.data_ptr(), adj.data_ptr(), _lib.ctypes.byref(gs), _lib.ptr(out[5]),
+        _lib.ptr(out[6]), ws.data_ptr(), _lib.stream_handle(dev)), "fetode_driven_param_grad")
+    return out
+
+
 class _DrivenFn(torch.autograd.Function):
     """Taped one-launch solve; backward = one reverse sweep (adjoints of every evaluation's output
     and of h0), then the parameter sums over the taped rows."""
@@ -692,20 +749,12 @@ class _DrivenFn(torch.autograd.Function):
             "fetode_driven_fixed_backward")
         want = ctx.needs_input_grad[4:]
         grads = [None] * 7
-        if any(want) and ne:
-            gain = params[5]
-            y = torch.tanh(tphi)
-            if any(want[:5]):
-                from .autograd_ops import _ferro_backward_generic
-                gphi = (adj * gain) * (1.0 - y * y)
-                prev = torch.cat([prev0.unsqueeze(0), thx[:-1]], dim=0)
-                _, fg = _ferro_backward_generic(f.basis, thx.view(ne * B, In), prev.view(ne * B, In), False, None,
-                                                gphi.view(ne * B, H), False, list(want[:5]))
-                grads[:5] = fg
-            if want[5]:
-                grads[5] = (adj * y).sum(dim=(0, 1))
-            if want[6]:
-                grads[6] = adj.sum(dim=(0, 1))
+        if any(want) and ne and _DRIVEN_PARAM_GRADS[0]:
+            grads = driven_param_grads(ctx.d, [_lib.f32c(p) for p in params], want, B, ne, 1, B, None, 0, prev0,
+                                       thx, tphi, adj)
+        elif any(want) and ne:
+            grads = _driven_param_sums_generic(f, params[5], want, thx, tphi, adj,
+                                               lambda: torch.cat([prev0.unsqueeze(0), thx[:-1]], dim=0))
         elif any(want):
             grads = [torch.zeros_like(p) if w else None for p, w in zip(params, want)]
         return (None, None, None, gh0 if ctx.needs_input_grad[3] else None, *grads)
@@ -977,25 +1026,21 @@ class _DrivenDopri5Fn(torch.autograd.Function):
         _DrivenDopri5Fn.last_adj = adj   # every evaluation's output adjoint (tests and tooling)
         want = ctx.needs_input_grad[8:]
         grads = [None] * 7
-        if any(want):
+        if any(want) and _DRIVEN_PARAM_GRADS[0]:
+            # the kernel walks sample b's rows below its own nfev (stats[b, 0]) and reads no others
+            ne = min(max(ctx.rec.nfev), tape.max_ev)
+            if ne > 0:
+                grads = driven_param_grads(ctx.d, [_lib.f32c(p) for p in params], want, B, ne, tape.max_ev, 1,
+                                           tape.stats, 3, ctx.prev0, tape.hx, tape.phi, adj)
+            else:
+                grads = [torch.zeros_like(p) if w else None for p, w in zip(params, want)]
+        elif any(want):
             # rows at or beyond a sample's nfev are zeros in the tape and in adj, so the sums may run over
             # the rows up to the batch's longest solve
             ne = max(ctx.rec.nfev)
             thx, tphi, adj = tape.hx[:, :ne], tape.phi[:, :ne], adj[:, :ne]
-            gain = params[5]
-            y = torch.tanh(tphi)
-            if any(want[:5]):
-                from .autograd_ops import _ferro_backward_generic
-                In = thx.shape[2]
-                gphi = (adj * gain) * (1.0 - y * y)
-                prev = tape_prev_rows(thx, ctx.prev0)
-                _, fg = _ferro_backward_generic(f.basis, thx.reshape(B * ne, In), prev.reshape(B * ne, In), False, None,
-                                                gphi.reshape(B * ne, H), False, list(want[:5]))
-                grads[:5] = fg
-            if want[5]:
-                grads[5] = (adj * y).sum(dim=(0, 1))
-            if want[6]:
-                grads[6] = adj.sum(dim=(0, 1))
+            grads = _driven_param_sums_generic(f, params[5], want, thx, tphi, adj,
+                                               lambda: tape_prev_rows(thx, ctx.prev0))
         return (None, None, None, gh0 if ctx.needs_input_grad[3] else None, None, None, None, None, *grads)
 
 

@@ -818,8 +818,9 @@ int fetode_driven_fixed_tape(const fetode_ferro_t* basis, const void* plan, int3
 /* Reverse sweep of a taped solve that started at evaluation 0: grad_sol (n_steps + 1, B, H) is
  * d loss / d every trajectory row (row 0 = h0); writes adj (4 n_steps, B, H) = d loss / d every
  * evaluation's output and grad_h0 (B, H).  The gate reads prev detached.  Parameter gradients are
- * not summed here: they are fetode_ferro_backward over the 4 n_steps * B taped rows with
- * g = adj * gain * (1 - tanh^2(tape_phi)), and row reductions for gain and bias. */
+ * not summed here: they are fetode_driven_param_grad over the taped rows, or fetode_ferro_backward
+ * over the 4 n_steps * B taped rows with g = adj * gain * (1 - tanh^2(tape_phi)) and row reductions
+ * for gain and bias. */
 int fetode_driven_fixed_backward(const fetode_ferro_t* basis, const void* plan, int32_t method, int64_t B,
                                  const float* dt, int32_t n_steps, const float* prev0, const float* tape_hx,
                                  const float* tape_phi, const float* grad_sol, float* adj, float* grad_h0,
@@ -868,7 +869,8 @@ int fetode_driven_dopri5_tape(const fetode_ferro_t* basis, const void* plan, con
  * t0 and stage time a constant; the evaluations of rejected attempts get exact zeros).  The gate
  * reads prev detached; x carries no adjoint.  A sample whose status is not 0, or whose attempts or
  * evaluations exceed max_attempts / max_ev, gets zeros.  Parameter gradients are not summed here:
- * they are fetode_ferro_backward over the B * max_ev taped rows (prev = the preceding row of the
+ * they are fetode_driven_param_grad over the live rows (nfev = stats), or
+ * fetode_ferro_backward over the B * max_ev taped rows (prev = the preceding row of the
  * same sample, prev0 for its row 0) with g = adj * gain * (1 - tanh^2(tape_phi)), and row reductions
  * for gain and bias.  opts, tableau, prev0 as given to the forward. */
 int fetode_driven_dopri5_backward(const fetode_ferro_t* basis, const void* plan, int64_t B, const float* t_grid,
@@ -877,6 +879,35 @@ int fetode_driven_dopri5_backward(const fetode_ferro_t* basis, const void* plan,
                                   int32_t max_attempts, const float* tape_hx, const float* tape_phi,
                                   const float* tape_slope, const double* init_rec, int32_t max_ev,
                                   const float* grad_sol, int32_t step_grad, float* adj, float* grad_h0, void* stream);
+/* The parameter gradients of a taped driven solve, summed on the device from the sweep's adj (one
+ * entry for both tapes).  Row (b, e), b < B, e < n_ev, of tape_hx / tape_phi / adj (H + D, H and H floats
+ * wide) sits at row index b * stride_b + e * stride_e: the rk4 tape (n_ev, B, .) is stride_b = 1,
+ * stride_e = B; the dopri5 tape (B, max_ev, .) is stride_b = max_ev, stride_e = 1.  nfev (nullable:
+ * every row is live) holds sample b's live-row count at nfev[b * nfev_stride] (stats (B, 3): stride 3);
+ * it is clamped to n_ev, a count <= 0 contributes nothing, and rows at or beyond it are not read at all.
+ * The hysteresis input of row (b, e) is row (b, e - 1) of tape_hx, for e = 0 prev0[b] (B, H + D;
+ * nullable = zeros, the reset state).  The output cotangent is formed here:
+ * g = adj * gain * (1 - tanh^2(tape_phi)).  Over the live rows: grads = the five Ferro sums
+ * (fetode_ferro_backward's, constant branch sign), g_gain (H) = sum adj * tanh(tape_phi), g_bias (H) =
+ * sum adj.  Every output pointer, each member of grads included, is nullable: a NULL output is neither
+ * computed into nor written; the others are overwritten.  Per-slice partial sums go to workspace
+ * (fetode_driven_param_grad_workspace bytes; -1 outside the family) and are added in a fixed order:
+ * the same bits from run to run, and for the same rows presented in either layout.
+ * FETODE_EUNSUPPORTED outside fetode_driven_supported (before any launch); B <= 0 or n_ev <= 0:
+ * FETODE_OK, nothing touched; FETODE_EINVAL: gain or a tape NULL, workspace NULL with an output
+ * requested, a stride < 1. */
+int64_t fetode_driven_param_grad_workspace(const fetode_ferro_t* basis, int64_t B, int64_t n_ev);
+int fetode_driven_param_grad(const fetode_ferro_t* basis, const float* gain, int64_t B, int64_t n_ev, int64_t stride_b,
+                             int64_t stride_e, const int32_t* nfev, int64_t nfev_stride, const float* prev0,
+                             const float* tape_hx, const float* tape_phi, const float* adj,
+                             const fetode_ferro_grad_t* grads, float* g_gain, float* g_bias, void* workspace,
+                             void* stream);
+/* The row split of fetode_driven_param_grad: 0 = from the shape, 1..64 forced; any other argument
+ * changes nothing (so a negative one is a query).  Returns the previous value.  A launch over
+ * R = B * n_ev rows uses at most max(1, min(64, R / 4)) slices, forced or not, and the workspace is sized
+ * for that many, each 3 * (in_dim * num_basis * out_dim + out_dim) floats: its size does not depend on
+ * this knob.  Process-wide tuning / test knob. */
+int fetode_driven_param_grad_set_splits(int s);
 
 #ifdef __cplusplus
 }
