@@ -329,6 +329,18 @@ SIGNATURES = {
                                                 ctypes.c_int64, ctypes.c_int64, _vp, ctypes.c_int64, _vp, _vp, _vp,
                                                 _vp, ctypes.POINTER(FerroGrad), _vp, _vp, _vp, _vp]),
     "fetode_driven_param_grad_set_splits": (ctypes.c_int, [ctypes.c_int]),
+    "fetode_driven_fixed_backward_x": (ctypes.c_int, [ctypes.POINTER(FerroDesc), _vp, ctypes.c_int32, ctypes.c_int64,
+                                                      _vp, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "fetode_driven_dopri5_backward_x": (ctypes.c_int, [ctypes.POINTER(FerroDesc), _vp, ctypes.c_int64, _vp,
+                                                       ctypes.c_int32, ctypes.c_double, ctypes.c_double,
+                                                       ctypes.POINTER(ctypes.c_double),
+                                                       ctypes.POINTER(ctypes.c_float), _vp, _vp, _vp, ctypes.c_int32,
+                                                       _vp, _vp, _vp, _vp, ctypes.c_int32, _vp, ctypes.c_int32, _vp,
+                                                       _vp, _vp, _vp]),
+    "fetode_driven_table_backward_workspace": (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int64]),
+    "fetode_driven_table_backward": (ctypes.c_int, [_vp, ctypes.c_int64, _vp, ctypes.c_int32, _vp, ctypes.c_int64,
+                                                    ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _vp,
+                                                    ctypes.c_int64, ctypes.c_int32, _vp, _vp, _vp]),
 }
 
 _lib: Optional[ctypes.CDLL] = None

@@ -45,6 +45,7 @@ struct DrivenAdjArgs {
   const float* grad_sol;  // (n_steps + 1, B, H): d loss / d every trajectory row, row 0 = h0
   float* adj;             // (4 n_steps, B, H): d loss / d every evaluation's output
   float* grad_h0;         // (B, H)
+  float* adj_u;           // (4 n_steps, B, D): d loss / d every evaluation's x(t); the XG kernels only
   int64_t B;
   int32_t H, D, K, n_steps;
   float gs, gsl2e, wc;

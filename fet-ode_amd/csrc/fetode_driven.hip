@@ -4,8 +4,11 @@
 //   driven_table_kernel   x(t) at every evaluation time, the reference's fp32 expression (:861-872)
 //   driven_plan_kernel    per-element constants + sum bias*coef per output, one launch
 //   driven_fixed_kernel   the whole fixed-grid solve; a workgroup owns its samples from h0 to the end
-//   driven_adj_kernel     the reverse sweep along the chain of evaluations (d/dh only; the parameter
-//                         sums over the taped rows: fetode_driven_pgrad.hip or the generic Ferro backward)
+//   driven_adj_kernel     the reverse sweep along the chain of evaluations (d/dh; with XG also d/dx(t)
+//                         of every evaluation; the parameter sums over the taped rows:
+//                         fetode_driven_pgrad.hip or the generic Ferro backward)
+//   driven_table_bwd_kernel  d/dx(t) of every evaluation back to the series' knots (LinearInterp1D's
+//                         backward), a gather in ascending evaluation order
 // The reference resets the hysteresis state before every sample's solve, so the samples are
 // independent: sample b carries its own driving row and its own prev.  branch_sign stays 1, so
 //     m = 1 - 2(1-alpha)(1-u) sigma(gs(-x-Ec)),   u = sigma(gs(x - prev))       (DESIGN §3 "Algebra").
@@ -43,6 +46,72 @@ __global__ __launch_bounds__(256) void driven_table_kernel(const float* __restri
     const float w = (t - t0) / ((t1 - t0) + 1e-12f);
     u[idx] = (1.0f - w) * x0 + w * x1;
   }
+}
+
+// ---------------------------------------------------------------------------------------------
+// driving table, backward: grad_x[b][j][d] = sum over sample b's live evaluations e, in ascending e,
+// of adj_u[b][e][d] times the weight the forward gave knot j at the evaluation's time
+// ---------------------------------------------------------------------------------------------
+constexpr int kTbThreads = 256;
+
+struct DrivenTbArgs {
+  const float* tq;        // the time of row (b, e) at tq[b * tq_stride_b + e]
+  const float* tg;        // (T) knots
+  const float* adj_u;     // row (b, e) at (b * stride_b + e * stride_e) * D
+  const int32_t* nfev;    // nullable: every row e < n_ev is live
+  float* gx;              // (B, T, D)
+  int64_t B, n_ev, tq_stride_b, stride_b, stride_e, nfev_stride;
+  int32_t T, D;
+};
+
+// Workgroup (b, chunk of 256 outputs): thread -> output (j, d) of sample b.  The sample's evaluations
+// are taken 256 at a time: every thread locates one of them in the grid (driven_table_kernel's fp32
+// expression: clamp, searchsorted left, clamp(1, T - 1), w from the clamped t) into LDS, then every
+// thread walks the 256 (interval, weight) pairs in order and adds the ones that name its knot.  The
+// order is ascending e whatever the strides are: the same bits for the same rows in either layout.
+__global__ __launch_bounds__(kTbThreads) void driven_table_bwd_kernel(DrivenTbArgs a) {
+  __shared__ int si[kTbThreads];
+  __shared__ float sw[kTbThreads];
+  const int tid = threadIdx.x, T = a.T, D = a.D;
+  const int64_t b = blockIdx.x;   // grid.x = B
+  const int64_t o = (int64_t)blockIdx.y * kTbThreads + tid;
+  const bool act = o < (int64_t)T * D;
+  const int j = act ? (int)(o / D) : 0, d = act ? (int)(o - (int64_t)j * D) : 0;
+  int64_t nl = a.n_ev;            // the live rows of sample b: min(nfev, n_ev), 0 for a count <= 0
+  if (a.nfev) {
+    const int64_t n = a.nfev[b * a.nfev_stride];
+    nl = n < 0 ? 0 : (n > a.n_ev ? a.n_ev : n);
+  }
+  const float* __restrict__ tg = a.tg;
+  const float lo = tg[0], hi = tg[T - 1];
+  float acc = 0.f;
+  for (int64_t e0 = 0; e0 < nl; e0 += kTbThreads) {   // nl is uniform: every thread reaches every barrier
+    const int64_t e = e0 + tid;
+    if (e < nl) {
+      float t = a.tq[b * a.tq_stride_b + e];
+      t = t < lo ? lo : (t > hi ? hi : t);
+      int i = 0;
+      for (int q = 0; q < T; ++q) i += tg[q] < t ? 1 : 0;
+      i = i < 1 ? 1 : (i > T - 1 ? T - 1 : i);
+      const float t0 = tg[i - 1], t1 = tg[i];
+      si[tid] = i;
+      sw[tid] = (t - t0) / ((t1 - t0) + 1e-12f);
+    }
+    __syncthreads();
+    const int n = nl - e0 < kTbThreads ? (int)(nl - e0) : kTbThreads;
+    if (act) {
+      for (int q = 0; q < n; ++q) {
+        const int i = si[q];
+        if (i == j || i - 1 == j) {   // 1 <= i <= T - 1: at most one of the two
+          const float w = sw[q];
+          const float g = a.adj_u[(b * a.stride_b + (e0 + q) * a.stride_e) * D + d];
+          acc = acc + (i == j ? w : 1.0f - w) * g;
+        }
+      }
+    }
+    __syncthreads();
+  }
+  if (act) a.gx[(b * T + j) * D + d] = acc;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -221,11 +290,15 @@ __device__ __forceinline__ float wave_sum(float v) {
   return v;
 }
 
-template <int S, int KT>
+// XG: the D driving inputs carry an adjoint too; adj_u (4 n_steps, B, D) receives it per evaluation.
+// The h inputs' arithmetic is the same either way, so adj and grad_h0 are the same bits.
+template <int S, int KT, bool XG>
 __global__ __launch_bounds__(kDrvThreads) void driven_adj_kernel(DrivenAdjArgs a) {
-  __shared__ float xs[S][kDrvHMax], gxs[S][kDrvHMax], vs[S][kDrvHMax], us[S][kDrvHMax];
-  __shared__ float gph[S][64], gout[S][kDrvHMax];
+  constexpr int NI = XG ? kDrvInMax : kDrvHMax;
+  __shared__ float xs[S][NI], gxs[S][NI], vs[S][NI], us[S][NI];
+  __shared__ float gph[S][64], gout[S][NI];
   const int H = a.H, D = a.D, In = H + D, K = KT > 0 ? KT : a.K;
+  const int nI = XG ? In : H;   // inputs that carry an adjoint
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int64_t B = a.B, b0 = (int64_t)blockIdx.x * S;
   const float4* __restrict__ el = reinterpret_cast<const float4*>(a.plan);
@@ -270,8 +343,8 @@ __global__ __launch_bounds__(kDrvThreads) void driven_adj_kernel(DrivenAdjArgs a
 #pragma unroll
       for (int s = 0; s < S; ++s) gph[s][lane] = 0.f;
     }
-    for (int idx = tid; idx < S * H; idx += kDrvThreads) {
-      const int s = idx / H, i = idx - s * H;
+    for (int idx = tid; idx < S * nI; idx += kDrvThreads) {
+      const int s = idx / nI, i = idx - s * nI;
       const int64_t b = b0 + s;
       float xv = 0.f, pv = 0.f;
       if (b < B) {
@@ -288,7 +361,7 @@ __global__ __launch_bounds__(kDrvThreads) void driven_adj_kernel(DrivenAdjArgs a
     float gp[S];
 #pragma unroll
     for (int s = 0; s < S; ++s) gp[s] = gph[s][lane];
-    for (int i = wv; i < H; i += 4) {   // only the h inputs carry an adjoint
+    for (int i = wv; i < nI; i += 4) {   // XG off: only the h inputs carry an adjoint
       float d[S];
 #pragma unroll
       for (int s = 0; s < S; ++s) d[s] = 0.f;
@@ -317,6 +390,12 @@ __global__ __launch_bounds__(kDrvThreads) void driven_adj_kernel(DrivenAdjArgs a
       }
     }
     __syncthreads();
+    if (XG) {
+      for (int idx = tid; idx < S * D; idx += kDrvThreads) {
+        const int s = idx / D, dd = idx - s * D;
+        if (b0 + s < B) a.adj_u[((int64_t)e * B + b0 + s) * D + dd] = gout[s][H + dd];
+      }
+    }
     if (own) {
 #pragma unroll
       for (int s = 0; s < S; ++s) {
@@ -379,17 +458,18 @@ void launch_fixed(int spw, int K, int64_t grid, hipStream_t st, const DrivenArgs
   else launch_fixed_s<4, TAPE>(K, grid, st, a);
 }
 
-template <int S>
+template <int S, bool XG>
 void launch_adj_s(int K, int64_t grid, hipStream_t st, const DrivenAdjArgs& a) {
   const dim3 g((unsigned)grid), t(kDrvThreads);
-  if (K == 10) hipLaunchKernelGGL((driven_adj_kernel<S, 10>), g, t, 0, st, a);
-  else if (K == 12) hipLaunchKernelGGL((driven_adj_kernel<S, 12>), g, t, 0, st, a);
-  else hipLaunchKernelGGL((driven_adj_kernel<S, 0>), g, t, 0, st, a);
+  if (K == 10) hipLaunchKernelGGL((driven_adj_kernel<S, 10, XG>), g, t, 0, st, a);
+  else if (K == 12) hipLaunchKernelGGL((driven_adj_kernel<S, 12, XG>), g, t, 0, st, a);
+  else hipLaunchKernelGGL((driven_adj_kernel<S, 0, XG>), g, t, 0, st, a);
 }
+template <bool XG>
 void launch_adj(int spw, int K, int64_t grid, hipStream_t st, const DrivenAdjArgs& a) {
-  if (spw == 1) launch_adj_s<1>(K, grid, st, a);
-  else if (spw == 2) launch_adj_s<2>(K, grid, st, a);
-  else launch_adj_s<4>(K, grid, st, a);
+  if (spw == 1) launch_adj_s<1, XG>(K, grid, st, a);
+  else if (spw == 2) launch_adj_s<2, XG>(K, grid, st, a);
+  else launch_adj_s<4, XG>(K, grid, st, a);
 }
 
 int driven_fixed(const fetode_ferro_t* fl, const void* plan, int32_t method, const float* h0, int64_t B, const float* u,
@@ -416,6 +496,32 @@ int driven_fixed(const fetode_ferro_t* fl, const void* plan, int32_t method, con
   a.wc = (float)(-2.0 * (1.0 - fl->alpha));
   if (tape) launch_fixed<true>(spw, a.K, grid, (hipStream_t)stream, a);
   else launch_fixed<false>(spw, a.K, grid, (hipStream_t)stream, a);
+  LAUNCH_CHECK();
+  return FETODE_OK;
+}
+
+int driven_backward(const fetode_ferro_t* basis, const void* plan, int32_t method, int64_t B, const float* dt,
+                    int32_t n_steps, const float* prev0, const float* tape_hx, const float* tape_phi,
+                    const float* grad_sol, float* adj, float* grad_h0, float* adj_u, bool xg, void* stream) {
+  if (!drv_shape_ok(basis)) return set_err(FETODE_EUNSUPPORTED, "driven: shape outside the admitted family");
+  if (method != FETODE_RK4) return set_err(FETODE_EUNSUPPORTED, "driven: only rk4 (3/8 rule) is fused");
+  if (B < 0 || n_steps < 0) return set_err(FETODE_EINVAL, "driven backward: bad sizes");
+  if (B == 0) return FETODE_OK;
+  if (!plan || !dt || !tape_hx || !tape_phi || !grad_sol || !adj || !grad_h0 || (xg && !adj_u))
+    return set_err(FETODE_EINVAL, "driven backward: null pointer");
+  const int spw = choose_spw(B);
+  const int64_t grid = (B + spw - 1) / spw;
+  if (grid > 0x7fffffff) return set_err(FETODE_EUNSUPPORTED, "driven: batch too large");
+  DrivenAdjArgs a{};
+  a.plan = (const float*)plan;
+  a.dt = dt; a.prev0 = prev0; a.tape_hx = tape_hx; a.tape_phi = tape_phi; a.grad_sol = grad_sol;
+  a.adj = adj; a.grad_h0 = grad_h0; a.adj_u = adj_u;
+  a.B = B;
+  a.H = basis->out_dim; a.D = basis->in_dim - basis->out_dim; a.K = basis->num_basis; a.n_steps = n_steps;
+  a.gs = (float)basis->gate_slope; a.gsl2e = (float)basis->gate_slope * FETODE_LOG2E;
+  a.wc = (float)(-2.0 * (1.0 - basis->alpha));
+  if (xg) launch_adj<true>(spw, a.K, grid, (hipStream_t)stream, a);
+  else launch_adj<false>(spw, a.K, grid, (hipStream_t)stream, a);
   LAUNCH_CHECK();
   return FETODE_OK;
 }
@@ -484,24 +590,42 @@ int fetode_driven_fixed_backward(const fetode_ferro_t* basis, const void* plan, 
                                  const float* dt, int32_t n_steps, const float* prev0, const float* tape_hx,
                                  const float* tape_phi, const float* grad_sol, float* adj, float* grad_h0,
                                  void* stream) {
-  if (!drv_shape_ok(basis)) return set_err(FETODE_EUNSUPPORTED, "driven: shape outside the admitted family");
-  if (method != FETODE_RK4) return set_err(FETODE_EUNSUPPORTED, "driven: only rk4 (3/8 rule) is fused");
-  if (B < 0 || n_steps < 0) return set_err(FETODE_EINVAL, "driven backward: bad sizes");
-  if (B == 0) return FETODE_OK;
-  if (!plan || !dt || !tape_hx || !tape_phi || !grad_sol || !adj || !grad_h0)
-    return set_err(FETODE_EINVAL, "driven backward: null pointer");
-  const int spw = choose_spw(B);
-  const int64_t grid = (B + spw - 1) / spw;
-  if (grid > 0x7fffffff) return set_err(FETODE_EUNSUPPORTED, "driven: batch too large");
-  DrivenAdjArgs a{};
-  a.plan = (const float*)plan;
-  a.dt = dt; a.prev0 = prev0; a.tape_hx = tape_hx; a.tape_phi = tape_phi; a.grad_sol = grad_sol;
-  a.adj = adj; a.grad_h0 = grad_h0;
-  a.B = B;
-  a.H = basis->out_dim; a.D = basis->in_dim - basis->out_dim; a.K = basis->num_basis; a.n_steps = n_steps;
-  a.gs = (float)basis->gate_slope; a.gsl2e = (float)basis->gate_slope * FETODE_LOG2E;
-  a.wc = (float)(-2.0 * (1.0 - basis->alpha));
-  launch_adj(spw, a.K, grid, (hipStream_t)stream, a);
+  return driven_backward(basis, plan, method, B, dt, n_steps, prev0, tape_hx, tape_phi, grad_sol, adj, grad_h0, nullptr,
+                         false, stream);
+}
+
+int fetode_driven_fixed_backward_x(const fetode_ferro_t* basis, const void* plan, int32_t method, int64_t B,
+                                   const float* dt, int32_t n_steps, const float* prev0, const float* tape_hx,
+                                   const float* tape_phi, const float* grad_sol, float* adj, float* grad_h0,
+                                   float* adj_u, void* stream) {
+  return driven_backward(basis, plan, method, B, dt, n_steps, prev0, tape_hx, tape_phi, grad_sol, adj, grad_h0, adj_u,
+                         true, stream);
+}
+
+int64_t fetode_driven_table_backward_workspace(int64_t B, int64_t n_ev) {
+  (void)B;
+  (void)n_ev;
+  return 0;  // the gather keeps its (interval, weight) pairs in LDS
+}
+
+int fetode_driven_table_backward(const float* tq, int64_t tq_stride_b, const float* t_grid, int32_t T,
+                                 const float* adj_u, int64_t B, int64_t n_ev, int64_t stride_b, int64_t stride_e,
+                                 const int32_t* nfev, int64_t nfev_stride, int32_t D, float* grad_x, void* workspace,
+                                 void* stream) {
+  (void)workspace;
+  if (T < 2 || D < 1) return set_err(FETODE_EINVAL, "driven table backward: bad sizes (T=%d, D=%d)", T, D);
+  if (B <= 0 || n_ev <= 0) return FETODE_OK;
+  if (!tq || !t_grid || !adj_u || !grad_x) return set_err(FETODE_EINVAL, "driven table backward: null pointer");
+  if (tq_stride_b < 0 || stride_b < 1 || stride_e < 1 || (nfev && nfev_stride < 1))
+    return set_err(FETODE_EINVAL, "driven table backward: strides must be positive (tq_stride_b: not negative)");
+  const int64_t chunks = ((int64_t)T * D + kTbThreads - 1) / kTbThreads;
+  if (B > 0x7fffffff || chunks > 65535) return set_err(FETODE_EUNSUPPORTED, "driven table backward: too large");
+  DrivenTbArgs a{};
+  a.tq = tq; a.tg = t_grid; a.adj_u = adj_u; a.nfev = nfev; a.gx = grad_x;
+  a.B = B; a.n_ev = n_ev; a.tq_stride_b = tq_stride_b; a.stride_b = stride_b; a.stride_e = stride_e;
+  a.nfev_stride = nfev_stride; a.T = T; a.D = D;
+  hipLaunchKernelGGL(driven_table_bwd_kernel, dim3((unsigned)B, (unsigned)chunks), dim3(kTbThreads), 0,
+                     (hipStream_t)stream, a);
   LAUNCH_CHECK();
   return FETODE_OK;
 }

@@ -15,11 +15,12 @@
 // (equal on all its lanes, sums by the forward's butterfly); the four waves share the evaluation's VJP
 // in driven_adj_kernel's mapping (lane -> output, wave w -> inputs i = w (mod 4), one wave sum per
 // input; the gate's x differentiated, prev detached), over the H state inputs, and over the D driving
-// inputs too when the step-size gradient is on.
+// inputs too when the step-size gradient is on or adj_u is asked for (fetode_driven_dopri5_backward_x:
+// d loss / d x(t) of every evaluation, which fetode_driven_table_backward takes to the series' knots).
 // step_grad = 0 freezes the step sequence: every dt, t0 and stage time is a constant, so there is no
 // control chain and no time adjoint, and a rejected attempt contributes exactly nothing.
-// Written: adj (B, max_ev, H) = d loss / d every evaluation's output (rows at or beyond nfev: zeros) and
-// grad_h0 (B, H).  The parameter sums are formed from adj and the tape by the caller
+// Written: adj (B, max_ev, H) = d loss / d every evaluation's output (rows at or beyond nfev: zeros),
+// grad_h0 (B, H) and, where given, adj_u (B, max_ev, D) (zeros likewise).  The parameter sums are formed from adj and the tape by the caller
 // (fetode_driven_param_grad, fetode_driven_pgrad.hip, or the generic Ferro backward).
 #include <string.h>
 
@@ -44,6 +45,7 @@ struct DrivenDopriAdjArgs {
   const float* gsol;      // (T, B, H) d loss / d solution
   float* adj;             // (B, max_ev, H)
   float* grad_h0;         // (B, H)
+  float* adj_u;           // (B, max_ev, D) nullable: d loss / d every evaluation's x(t)
   int32_t H, D, K, T, max_att, max_ev, base, step_grad;
   float gs, gsl2e, wc;
   float rtol, atol;
@@ -83,6 +85,9 @@ __global__ __launch_bounds__(kDrvThreads) void driven_dopri5_adj_kernel(DrivenDo
   const int n_ev = ok ? nfev : 0;
   float* __restrict__ adjb = a.adj + b * (int64_t)max_ev * H;
   for (int64_t i = (int64_t)n_ev * H + tid; i < (int64_t)max_ev * H; i += kDrvThreads) adjb[i] = 0.f;
+  float* __restrict__ adjub = a.adj_u ? a.adj_u + b * (int64_t)max_ev * D : nullptr;
+  if (adjub)
+    for (int64_t i = (int64_t)n_ev * D + tid; i < (int64_t)max_ev * D; i += kDrvThreads) adjub[i] = 0.f;
   if (!ok) {
     if (tid < H) a.grad_h0[b * H + tid] = 0.f;
     return;
@@ -99,7 +104,7 @@ __global__ __launch_bounds__(kDrvThreads) void driven_dopri5_adj_kernel(DrivenDo
   const float rtol = a.rtol, atol = a.atol;
   const double n_el = (double)H;
   const float gain = own ? tail[H + lane] : 0.f, bias = own ? tail[2 * H + lane] : 0.f;
-  const int nI = sg ? In : H;  // inputs that carry an adjoint
+  const int nI = (sg || adjub) ? In : H;  // inputs that carry an adjoint
   if (tid == 0) {
 #pragma unroll
     for (int i = 0; i < 6; ++i) {
@@ -318,6 +323,7 @@ __global__ __launch_bounds__(kDrvThreads) void driven_dopri5_adj_kernel(DrivenDo
       if (lane == 0) gout[i] = r * (0.5f / FETODE_LOG2E);  // c.y, c.z carry 2 log2e
     }
     __syncthreads();
+    if (adjub && tid >= 64 && tid < 64 + D) adjub[(int64_t)ev * D + (tid - 64)] = gout[H + (tid - 64)];
     // ---------------- after the VJP: the input adjoint (wave 0) ----------------
     if (w0) {
       const float xb = own ? gout[lane] : 0.f;
@@ -376,23 +382,19 @@ void launch_adj(int K, int64_t B, hipStream_t st, const DrivenDopriAdjArgs& a) {
   else hipLaunchKernelGGL((driven_dopri5_adj_kernel<0>), g, t, 0, st, a);
 }
 
-}  // namespace
-
-extern "C" {
-
-int fetode_driven_dopri5_backward(const fetode_ferro_t* basis, const void* plan, int64_t B, const float* t_grid,
-                                  int32_t T, double rtol, double atol, const double* opts, const float* tableau,
-                                  const float* prev0, const int32_t* stats, const double* attempts,
-                                  int32_t max_attempts, const float* tape_hx, const float* tape_phi,
-                                  const float* tape_slope, const double* init_rec, int32_t max_ev,
-                                  const float* grad_sol, int32_t step_grad, float* adj, float* grad_h0, void* stream) {
+int driven_dopri5_backward(const fetode_ferro_t* basis, const void* plan, int64_t B, const float* t_grid, int32_t T,
+                           double rtol, double atol, const double* opts, const float* tableau, const float* prev0,
+                           const int32_t* stats, const double* attempts, int32_t max_attempts, const float* tape_hx,
+                           const float* tape_phi, const float* tape_slope, const double* init_rec, int32_t max_ev,
+                           const float* grad_sol, int32_t step_grad, float* adj, float* grad_h0, float* adj_u, bool xg,
+                           void* stream) {
   if (!fetode_driven_supported(basis)) return set_err(FETODE_EUNSUPPORTED, "driven: shape outside the admitted family");
   if (B < 0 || T < 2 || max_attempts < 1 || max_ev < 1)
     return set_err(FETODE_EINVAL, "driven dopri5 backward: bad sizes (B=%lld, T=%d, max_attempts=%d, max_ev=%d)",
                    (long long)B, T, max_attempts, max_ev);
   if (B == 0) return FETODE_OK;
   if (!plan || !t_grid || !opts || !tableau || !stats || !attempts || !tape_hx || !tape_phi || !tape_slope ||
-      !init_rec || !grad_sol || !adj || !grad_h0)
+      !init_rec || !grad_sol || !adj || !grad_h0 || (xg && !adj_u))
     return set_err(FETODE_EINVAL, "driven dopri5 backward: null pointer");
   if (B > 0x7fffffff) return set_err(FETODE_EUNSUPPORTED, "driven dopri5: batch too large");
   DrivenDopriAdjArgs a{};
@@ -401,7 +403,7 @@ int fetode_driven_dopri5_backward(const fetode_ferro_t* basis, const void* plan,
   a.plan = (const float*)plan;
   a.tg = t_grid; a.prev0 = prev0; a.stats = stats; a.att = attempts; a.init_rec = init_rec;
   a.tape_hx = tape_hx; a.tape_phi = tape_phi; a.tape_sl = tape_slope; a.gsol = grad_sol;
-  a.adj = adj; a.grad_h0 = grad_h0;
+  a.adj = adj; a.grad_h0 = grad_h0; a.adj_u = adj_u;
   a.H = basis->out_dim; a.D = basis->in_dim - basis->out_dim; a.K = basis->num_basis; a.T = T;
   a.max_att = max_attempts; a.max_ev = max_ev; a.base = dopri_base(opts); a.step_grad = step_grad ? 1 : 0;
   a.gs = (float)basis->gate_slope; a.gsl2e = (float)basis->gate_slope * FETODE_LOG2E;
@@ -416,6 +418,33 @@ int fetode_driven_dopri5_backward(const fetode_ferro_t* basis, const void* plan,
   launch_adj(a.K, B, (hipStream_t)stream, a);
   LAUNCH_CHECK();
   return FETODE_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fetode_driven_dopri5_backward(const fetode_ferro_t* basis, const void* plan, int64_t B, const float* t_grid,
+                                  int32_t T, double rtol, double atol, const double* opts, const float* tableau,
+                                  const float* prev0, const int32_t* stats, const double* attempts,
+                                  int32_t max_attempts, const float* tape_hx, const float* tape_phi,
+                                  const float* tape_slope, const double* init_rec, int32_t max_ev,
+                                  const float* grad_sol, int32_t step_grad, float* adj, float* grad_h0, void* stream) {
+  return driven_dopri5_backward(basis, plan, B, t_grid, T, rtol, atol, opts, tableau, prev0, stats, attempts,
+                                max_attempts, tape_hx, tape_phi, tape_slope, init_rec, max_ev, grad_sol, step_grad, adj,
+                                grad_h0, nullptr, false, stream);
+}
+
+int fetode_driven_dopri5_backward_x(const fetode_ferro_t* basis, const void* plan, int64_t B, const float* t_grid,
+                                    int32_t T, double rtol, double atol, const double* opts, const float* tableau,
+                                    const float* prev0, const int32_t* stats, const double* attempts,
+                                    int32_t max_attempts, const float* tape_hx, const float* tape_phi,
+                                    const float* tape_slope, const double* init_rec, int32_t max_ev,
+                                    const float* grad_sol, int32_t step_grad, float* adj, float* grad_h0,
+                                    float* adj_u, void* stream) {
+  return driven_dopri5_backward(basis, plan, B, t_grid, T, rtol, atol, opts, tableau, prev0, stats, attempts,
+                                max_attempts, tape_hx, tape_phi, tape_slope, init_rec, max_ev, grad_sol, step_grad, adj,
+                                grad_h0, adj_u, true, stream);
 }
 
 }  // extern "C"

@@ -408,6 +408,9 @@ class KanFet_MLP_NODE(CacheFreeState, nn.Module):
 # slow path); with set_resident_driven_dopri5_training(True) it is the taped launch and one reverse
 # sweep (fetode_driven_dopri5_tape / _backward), whose gradient runs through dt into
 # x(t) like autograd's does — or, with step_grad=False, treats the step sequence as constants.
+# A driving series that requires grad leaves both taped paths (per-stage rk4, per-sample dopri5 loop)
+# unless set_driven_series_grad(True): then the sweeps also form d loss / d x(t) per evaluation and
+# fetode_driven_table_backward gathers it onto the series' knots.
 # Both taped backwards form the parameter gradients from the sweep's adj: by default with the generic
 # Ferro backward over every taped row and two torch reductions, with set_fused_driven_param_grads(True)
 # in one driven-field kernel over the live rows (fetode_driven_param_grad).
@@ -418,6 +421,7 @@ _DRIVEN_MAX_TRACE = 1024   # attempts logged per sample (the count itself is exa
 _DRIVEN_DOPRI5_TRAIN = [_lib.os.environ.get("FETODE_DRIVEN_DOPRI5_TRAIN", "0") == "1", True]   # enabled, step_grad
 _DRIVEN_TAPE_ATTEMPTS = 64   # attempts per sample the first taped launch has room for
 _DRIVEN_PARAM_GRADS = [_lib.os.environ.get("FETODE_DRIVEN_PARAM_GRADS", "0") == "1"]
+_DRIVEN_XGRAD = [_lib.os.environ.get("FETODE_DRIVEN_XGRAD", "0") == "1"]
 
 
 def set_fused_driven(enabled: bool) -> bool:
@@ -456,6 +460,17 @@ def set_fused_driven_param_grads(enabled: bool) -> bool:
     Ferro backward over every taped row plus two torch reductions (default off; env
     FETODE_DRIVEN_PARAM_GRADS=1 turns it on).  Returns the previous value."""
     prev, _DRIVEN_PARAM_GRADS[0] = _DRIVEN_PARAM_GRADS[0], bool(enabled)
+    return prev
+
+
+def set_driven_series_grad(enabled: bool) -> bool:
+    """Keep a driving series that requires grad on the one-launch solves (rk4, and dopri5 where
+    set_resident_driven_dopri5_training is on): the reverse sweep also forms d loss / d x(t) of every
+    evaluation (fetode_driven_fixed_backward_x / fetode_driven_dopri5_backward_x) and
+    fetode_driven_table_backward takes it to the series' knots, instead of the per-stage
+    path (rk4) or the per-sample host loop (dopri5) (default off; env FETODE_DRIVEN_XGRAD=1 turns it
+    on).  Returns the previous value."""
+    prev, _DRIVEN_XGRAD[0] = _DRIVEN_XGRAD[0], bool(enabled)
     return prev
 
 
@@ -625,7 +640,8 @@ def _driven_rules(func, t, tc, reversed_) -> bool:
 def driven_recognise(func, y0, t, tc, step_size, reversed_, method_code):
     """(x (B, T, D), grid tensors) of a solve the fused driven path reproduces, or None:
     driven_eligible, and every tensor fp32 on y0's GPU with matching shapes; a driving series that
-    requires grad is left to the per-stage path (the sweep carries no adjoint to x(t))."""
+    requires grad is left to the per-stage path unless set_driven_series_grad is on, and is then
+    returned attached (a 2-D series as its expand over the batch, so autograd sums the rows)."""
     if y0.dim() != 2 or y0.dtype != torch.float32 or not y0.is_cuda:
         return None
     if not driven_eligible(func, t, tc, step_size, reversed_, method_code):
@@ -638,11 +654,12 @@ def driven_recognise(func, y0, t, tc, step_size, reversed_, method_code):
     if (x.dim() != 3 or x.shape[0] != B or x.shape[1] != tg.numel() or x.shape[2] != bas.in_dim - bas.out_dim
             or H != bas.out_dim or x.dtype != torch.float32 or x.device != y0.device):
         return None
-    if torch.is_grad_enabled() and x.requires_grad:
+    xgrad = torch.is_grad_enabled() and x.requires_grad
+    if xgrad and not _DRIVEN_XGRAD[0]:
         return None
     if any(p.device != y0.device or p.dtype != torch.float32 for p in _driven_tensors(func)):
         return None
-    return x.detach().contiguous(), _driven_grid(tc, y0.device)
+    return (x if xgrad else x.detach().contiguous()), _driven_grid(tc, y0.device)
 
 
 def _driven_prev0(f, h0, u):
@@ -694,6 +711,23 @@ def _driven_param_sums_generic(f, gain, want, thx, tphi, adj, prev_rows):
     return grads
 
 
+def driven_series_grad(tq, tq_stride_b, t_grid, adj_u, B, n_ev, stride_b, stride_e, nfev, nfev_stride, D):
+    """grad_x (B, T, D) from the sweep's adj_u in one call of fetode_driven_table_backward (LinearInterp1D's
+    backward): row (b, e) of adj_u at row b * stride_b + e * stride_e, its time at tq[b * tq_stride_b + e],
+    nfev (int32, nullable) sample b's live rows at nfev[b * nfev_stride]."""
+    lib = _lib.load()
+    dev = adj_u.device
+    T = t_grid.numel()
+    gx = torch.zeros(B, T, D, device=dev, dtype=torch.float32) if n_ev <= 0 else \
+        torch.empty(B, T, D, device=dev, dtype=torch.float32)
+    nb = lib.fetode_driven_table_backward_workspace(B, n_ev)
+    ws = torch.empty(nb // 4, device=dev, dtype=torch.float32) if nb > 0 else None
+    _lib.check(lib.fetode_driven_table_backward(
+        tq.data_ptr(), tq_stride_b, t_grid.data_ptr(), T, adj_u.data_ptr(), B, n_ev, stride_b, stride_e, _lib.ptr(nfev),
+        nfev_stride, D, gx.data_ptr(), _lib.ptr(ws), _lib.stream_handle(dev)), "fetode_driven_table_backward")
+    return gx
+
+
 def driven_param_grads(d, params, want, B, n_ev, stride_b, stride_e, nfev, nfev_stride, prev0, thx, tphi, adj):
     """The seven parameter gradients (k, Ec, Ps, bias, coef, gain, bias; None where want is false) of
     a taped driven solve in one call of fetode_driven_param_grad: d the basis descriptor, params the
@@ -716,7 +750,8 @@ def driven_param_grads(d, params, want, B, n_ev, stride_b, stride_e, nfev, nfev_
 
 class _DrivenFn(torch.autograd.Function):
     """Taped one-launch solve; backward = one reverse sweep (adjoints of every evaluation's output
-    and of h0), then the parameter sums over the taped rows."""
+    and of h0 — and, where the series x (B, T, D) requires grad, of every evaluation's x(t), taken to
+    the knots by driven_series_grad), then the parameter sums over the taped rows."""
 
     @staticmethod
     def forward(ctx, f, x, grids, h0, *params):
@@ -724,11 +759,11 @@ class _DrivenFn(torch.autograd.Function):
         _, tq, dtv = grids
         plan, d, keep = _driven_plan(f, dev)
         h0c = _lib.f32c(h0)
-        u = driven_table(grids[0], x, tq)
+        u = driven_table(grids[0], _lib.f32c(x), tq)
         prev0 = _driven_prev0(f, h0c, u)
         n_steps = dtv.numel()
         sol, thx, tphi = _driven_launch(f, plan, d, h0c, u, dtv, prev0, n_steps, True)
-        ctx.f, ctx.plan, ctx.d, ctx.keep, ctx.n_steps = f, plan, d, keep, n_steps
+        ctx.f, ctx.plan, ctx.d, ctx.keep, ctx.n_steps, ctx.grids = f, plan, d, keep, n_steps, grids
         ctx.save_for_backward(dtv, prev0, thx, tphi, *[p.detach() for p in params])
         return sol
 
@@ -743,10 +778,18 @@ class _DrivenFn(torch.autograd.Function):
         In = thx.shape[2]
         adj = torch.empty_like(tphi)
         gh0 = torch.empty(B, H, device=dev, dtype=torch.float32)
-        _lib.check(lib.fetode_driven_fixed_backward(
-            _lib.ctypes.byref(ctx.d), ctx.plan.data_ptr(), _lib.RK4, B, dtv.data_ptr(), n_steps, prev0.data_ptr(),
-            thx.data_ptr(), tphi.data_ptr(), g.data_ptr(), adj.data_ptr(), gh0.data_ptr(), _lib.stream_handle(dev)),
-            "fetode_driven_fixed_backward")
+        args = [_lib.ctypes.byref(ctx.d), ctx.plan.data_ptr(), _lib.RK4, B, dtv.data_ptr(), n_steps, prev0.data_ptr(),
+                thx.data_ptr(), tphi.data_ptr(), g.data_ptr(), adj.data_ptr(), gh0.data_ptr()]
+        gx = None
+        if ctx.needs_input_grad[1]:
+            D = In - H
+            adj_u = torch.empty(ne, B, D, device=dev, dtype=torch.float32)
+            _lib.check(lib.fetode_driven_fixed_backward_x(*args, adj_u.data_ptr(), _lib.stream_handle(dev)),
+                       "fetode_driven_fixed_backward_x")
+            tg, tq, _ = ctx.grids
+            gx = driven_series_grad(tq, 0, tg, adj_u, B, ne, 1, B, None, 0, D)
+        else:
+            _lib.check(lib.fetode_driven_fixed_backward(*args, _lib.stream_handle(dev)), "fetode_driven_fixed_backward")
         want = ctx.needs_input_grad[4:]
         grads = [None] * 7
         if any(want) and ne and _DRIVEN_PARAM_GRADS[0]:
@@ -757,7 +800,7 @@ class _DrivenFn(torch.autograd.Function):
                                                lambda: torch.cat([prev0.unsqueeze(0), thx[:-1]], dim=0))
         elif any(want):
             grads = [torch.zeros_like(p) if w else None for p, w in zip(params, want)]
-        return (None, None, None, gh0 if ctx.needs_input_grad[3] else None, *grads)
+        return (None, gx, None, gh0 if ctx.needs_input_grad[3] else None, *grads)
 
 
 def driven_solve(func, y0, t, tc, step_size, reversed_, method_code):
@@ -770,7 +813,7 @@ def driven_solve(func, y0, t, tc, step_size, reversed_, method_code):
     if ent is None:
         return None
     params = _driven_tensors(func)
-    if torch.is_grad_enabled() and (y0.requires_grad or any(p.requires_grad for p in params)):
+    if torch.is_grad_enabled() and (x.requires_grad or y0.requires_grad or any(p.requires_grad for p in params)):
         return _DrivenFn.apply(func, x, grids, y0, *params)
     plan, d, _ = ent
     h0 = _lib.f32c(y0)
@@ -982,7 +1025,9 @@ class _TapeDeclined(Exception):
 class _DrivenDopri5Fn(torch.autograd.Function):
     """Taped one-launch dopri5 solve with a step controller per sample; backward = one reverse sweep
     (adjoints of every evaluation's output and of h0, through the step control unless step_grad is
-    off), then the parameter sums over the taped rows as in _DrivenFn.  reset: the rows start from the
+    off; where the series x (B, T, D) requires grad, also d loss / d every evaluation's x(t), taken to the
+    knots by driven_series_grad at the taped times), then the parameter sums over the taped rows as in
+    _DrivenFn.  reset: the rows start from the
     reset hysteresis state.  A failing sample raises in forward; the record of the last forward is
     _DrivenDopri5Fn.last, the adj (B, max_ev, H) of the last backward _DrivenDopri5Fn.last_adj."""
 
@@ -1016,13 +1061,24 @@ class _DrivenDopri5Fn(torch.autograd.Function):
         T, B, H = g.shape
         adj = torch.empty_like(tape.phi)
         gh0 = torch.empty(B, H, device=dev, dtype=torch.float32)
-        _lib.check(_lib.load().fetode_driven_dopri5_backward(
-            _lib.ctypes.byref(ctx.d), ctx.plan.data_ptr(), B, ctx.tg.data_ptr(), T, ctx.tols[0], ctx.tols[1],
-            tape.opts.ctypes.data_as(_lib.ctypes.POINTER(_lib.ctypes.c_double)),
-            _TABLEAU.ctypes.data_as(_lib.ctypes.POINTER(_lib.ctypes.c_float)), _lib.ptr(ctx.prev0),
-            tape.stats.data_ptr(), tape.att.data_ptr(), tape.max_att, tape.hx.data_ptr(), tape.phi.data_ptr(),
-            tape.slope.data_ptr(), tape.init.data_ptr(), tape.max_ev, g.data_ptr(), int(ctx.step_grad),
-            adj.data_ptr(), gh0.data_ptr(), _lib.stream_handle(dev)), "fetode_driven_dopri5_backward")
+        args = [_lib.ctypes.byref(ctx.d), ctx.plan.data_ptr(), B, ctx.tg.data_ptr(), T, ctx.tols[0], ctx.tols[1],
+                tape.opts.ctypes.data_as(_lib.ctypes.POINTER(_lib.ctypes.c_double)),
+                _TABLEAU.ctypes.data_as(_lib.ctypes.POINTER(_lib.ctypes.c_float)), _lib.ptr(ctx.prev0),
+                tape.stats.data_ptr(), tape.att.data_ptr(), tape.max_att, tape.hx.data_ptr(), tape.phi.data_ptr(),
+                tape.slope.data_ptr(), tape.init.data_ptr(), tape.max_ev, g.data_ptr(), int(ctx.step_grad),
+                adj.data_ptr(), gh0.data_ptr()]
+        gx = None
+        if ctx.needs_input_grad[1]:
+            D = tape.slope.shape[2]
+            adj_u = torch.empty(B, tape.max_ev, D, device=dev, dtype=torch.float32)
+            _lib.check(_lib.load().fetode_driven_dopri5_backward_x(*args, adj_u.data_ptr(), _lib.stream_handle(dev)),
+                       "fetode_driven_dopri5_backward_x")
+            # the gather walks sample b's rows below its own nfev (stats[b, 0]) and reads no others
+            gx = driven_series_grad(tape.t, tape.max_ev, ctx.tg, adj_u, B, min(max(ctx.rec.nfev), tape.max_ev),
+                                    tape.max_ev, 1, tape.stats, 3, D)
+        else:
+            _lib.check(_lib.load().fetode_driven_dopri5_backward(*args, _lib.stream_handle(dev)),
+                       "fetode_driven_dopri5_backward")
         _DrivenDopri5Fn.last_adj = adj   # every evaluation's output adjoint (tests and tooling)
         want = ctx.needs_input_grad[8:]
         grads = [None] * 7
@@ -1041,14 +1097,14 @@ class _DrivenDopri5Fn(torch.autograd.Function):
             thx, tphi, adj = tape.hx[:, :ne], tape.phi[:, :ne], adj[:, :ne]
             grads = _driven_param_sums_generic(f, params[5], want, thx, tphi, adj,
                                                lambda: tape_prev_rows(thx, ctx.prev0))
-        return (None, None, None, gh0 if ctx.needs_input_grad[3] else None, None, None, None, None, *grads)
+        return (None, gx, None, gh0 if ctx.needs_input_grad[3] else None, None, None, None, None, *grads)
 
 
 def driven_dopri5_train(func, y0, tc, reversed_, rtol, atol, options, reset=False, t=None):
     """The taped one-launch dopri5 solve under autograd, when set_resident_driven_dopri5_training is on:
     (solution (T, B, H) with a grad_fn, DrivenDopri5Solve), or None where the solve is not the
-    kernel's (driven_dopri5_solve's rules), nothing requires grad, or the driving series does (the
-    sweep carries no adjoint to x).  One step controller per row of y0, as in driven_dopri5_solve.
+    kernel's (driven_dopri5_solve's rules), nothing requires grad, or the driving series does while
+    set_driven_series_grad is off.  One step controller per row of y0, as in driven_dopri5_solve.
     A failing sample raises torchdiffeq's assertion, naming it."""
     if not _DRIVEN_DOPRI5_TRAIN[0] or not torch.is_grad_enabled():
         return None
@@ -1056,12 +1112,14 @@ def driven_dopri5_train(func, y0, tc, reversed_, rtol, atol, options, reset=Fals
     if rec is None:
         return None
     x, tg, params = rec
-    if x.requires_grad or not (y0.requires_grad or any(p.requires_grad for p in params)):
+    if x.requires_grad and not _DRIVEN_XGRAD[0]:
+        return None
+    if not (x.requires_grad or y0.requires_grad or any(p.requires_grad for p in params)):
         return None
     if _driven_plan(func, y0.device) is None:
         return None
     try:
-        sol = _DrivenDopri5Fn.apply(func, x.detach(), tg, y0, rtol, atol, dict(options), bool(reset), *params)
+        sol = _DrivenDopri5Fn.apply(func, x, tg, y0, rtol, atol, dict(options), bool(reset), *params)
     except _TapeDeclined:
         return None
     return sol, _DrivenDopri5Fn.last
@@ -1087,12 +1145,13 @@ class OneODEEncoder(CacheFreeState, nn.Module):
     def _solve_dopri5(self, xb, t_grid):
         """The whole batch under dopri5 in one launch, a step controller per sample, when the solve is the
         kernel's and nothing needs a gradient — or, with set_resident_driven_dopri5_training on, the
-        parameters or lift do (the taped launch, B >= 1) but the series does not; None otherwise (_solve then starts over: it sets the
-        interpolator and resets the state itself)."""
+        parameters or lift do (the taped launch, B >= 1) — the series too where set_driven_series_grad is
+        on; None otherwise (_solve then starts over: it sets the interpolator and resets the state
+        itself)."""
         if not _DRIVEN_DOPRI5:
             return None
         train = torch.is_grad_enabled() and (xb.requires_grad or any(p.requires_grad for p in self.parameters()))
-        if train and (xb.requires_grad or not _DRIVEN_DOPRI5_TRAIN[0]):
+        if train and ((xb.requires_grad and not _DRIVEN_XGRAD[0]) or not _DRIVEN_DOPRI5_TRAIN[0]):
             return None
         f = self.odefunc
         if not hasattr(f.basis, "reset_state"):

@@ -825,6 +825,33 @@ int fetode_driven_fixed_backward(const fetode_ferro_t* basis, const void* plan, 
                                  const float* dt, int32_t n_steps, const float* prev0, const float* tape_hx,
                                  const float* tape_phi, const float* grad_sol, float* adj, float* grad_h0,
                                  void* stream);
+/* The same sweep, which also writes adj_u (4 n_steps, B, D) = d loss / d every evaluation's x(t) (the
+ * Ferro VJP over the D driving inputs as well; must not be NULL).  adj and grad_h0 are bitwise
+ * fetode_driven_fixed_backward's.  fetode_driven_table_backward takes adj_u to the series. */
+int fetode_driven_fixed_backward_x(const fetode_ferro_t* basis, const void* plan, int32_t method, int64_t B,
+                                   const float* dt, int32_t n_steps, const float* prev0, const float* tape_hx,
+                                   const float* tape_phi, const float* grad_sol, float* adj, float* grad_h0,
+                                   float* adj_u, void* stream);
+/* LinearInterp1D's backward: grad_x (B, T, D) = d loss / d the driving series from adj_u = d loss / d
+ * every evaluation's x(t).  Row (b, e), b < B, e < n_ev, of adj_u (D floats wide) sits at row index
+ * b * stride_b + e * stride_e and its time at tq[b * tq_stride_b + e]: the rk4 sweep's adj_u
+ * (n_ev, B, D) with the shared stage times is tq_stride_b = 0, stride_b = 1, stride_e = B; the dopri5
+ * sweep's (B, max_ev, D) with tq = tape_t is tq_stride_b = stride_b = max_ev, stride_e = 1, nfev =
+ * stats with stride 3.  nfev (nullable: every row is live) as in fetode_driven_param_grad: clamped to
+ * n_ev, a count <= 0 contributes nothing, rows (and times) at or beyond it are not read.  Per row the
+ * forward's fp32 expression is recomputed (clamp, searchsorted left, clamp(1, T - 1),
+ * w = (t - t0) / (t1 - t0 + 1e-12) from the clamped t); knot i - 1 receives (1 - w) g and knot i
+ * receives w g, which is autograd's result (the time carries no adjoint here).  A gather: every knot
+ * adds its rows in ascending e, no atomics, so the bits are the same from run to run and for the same
+ * rows in either layout.  All of grad_x is overwritten (a knot nothing touches: 0).  workspace:
+ * fetode_driven_table_backward_workspace bytes (0 today: NULL is accepted).  T < 2, D < 1: FETODE_EINVAL;
+ * B <= 0 or n_ev <= 0: FETODE_OK, nothing touched; FETODE_EINVAL: a NULL pointer, stride_b or
+ * stride_e < 1, tq_stride_b < 0, nfev_stride < 1 with nfev; all decided before the launch. */
+int64_t fetode_driven_table_backward_workspace(int64_t B, int64_t n_ev);
+int fetode_driven_table_backward(const float* tq, int64_t tq_stride_b, const float* t_grid, int32_t T,
+                                 const float* adj_u, int64_t B, int64_t n_ev, int64_t stride_b, int64_t stride_e,
+                                 const int32_t* nfev, int64_t nfev_stride, int32_t D, float* grad_x, void* workspace,
+                                 void* stream);
 /* The same field under torchdiffeq's dopri5 over the output times t_grid (T >= 2, fp32, increasing:
  * the interpolator's own knots), the whole batch in one launch with one step controller PER SAMPLE:
  * sample b's error norm runs over its own H elements, so it takes the steps the reference's solve of
@@ -867,7 +894,7 @@ int fetode_driven_dopri5_tape(const fetode_ferro_t* basis, const void* plan, con
  * control, initial-step selection, and the evaluation times' adjoint through the slope of x(t));
  * step_grad == 0: the gradient of the discrete solve on the step sequence the forward took (every dt,
  * t0 and stage time a constant; the evaluations of rejected attempts get exact zeros).  The gate
- * reads prev detached; x carries no adjoint.  A sample whose status is not 0, or whose attempts or
+ * reads prev detached; the adjoint of x(t) is fetode_driven_dopri5_backward_x's.  A sample whose status is not 0, or whose attempts or
  * evaluations exceed max_attempts / max_ev, gets zeros.  Parameter gradients are not summed here:
  * they are fetode_driven_param_grad over the live rows (nfev = stats), or
  * fetode_ferro_backward over the B * max_ev taped rows (prev = the preceding row of the
@@ -879,6 +906,19 @@ int fetode_driven_dopri5_backward(const fetode_ferro_t* basis, const void* plan,
                                   int32_t max_attempts, const float* tape_hx, const float* tape_phi,
                                   const float* tape_slope, const double* init_rec, int32_t max_ev,
                                   const float* grad_sol, int32_t step_grad, float* adj, float* grad_h0, void* stream);
+/* The same sweep, which also writes adj_u (B, max_ev, D) = d loss / d every evaluation's x(t) (must
+ * not be NULL): the Ferro VJP runs over the D driving inputs whatever step_grad is.  Rows at or beyond
+ * nfev, and every row of a sample that gets zeros above, are zeros; with step_grad == 0 the
+ * evaluations of rejected attempts give exact zeros.  With step_grad != 0 the time's dependence on the
+ * series runs through adj like every other path.  adj and grad_h0 are bitwise
+ * fetode_driven_dopri5_backward's.  fetode_driven_table_backward (tq = tape_t) takes adj_u to the series. */
+int fetode_driven_dopri5_backward_x(const fetode_ferro_t* basis, const void* plan, int64_t B, const float* t_grid,
+                                    int32_t T, double rtol, double atol, const double* opts, const float* tableau,
+                                    const float* prev0, const int32_t* stats, const double* attempts,
+                                    int32_t max_attempts, const float* tape_hx, const float* tape_phi,
+                                    const float* tape_slope, const double* init_rec, int32_t max_ev,
+                                    const float* grad_sol, int32_t step_grad, float* adj, float* grad_h0,
+                                    float* adj_u, void* stream);
 /* The parameter gradients of a taped driven solve, summed on the device from the sweep's adj (one
  * entry for both tapes).  Row (b, e), b < B, e < n_ev, of tape_hx / tape_phi / adj (H + D, H and H floats
  * wide) sits at row index b * stride_b + e * stride_e: the rk4 tape (n_ev, B, .) is stride_b = 1,
