@@ -337,6 +337,15 @@ SIGNATURES = {
                                                        ctypes.POINTER(ctypes.c_float), _vp, _vp, _vp, ctypes.c_int32,
                                                        _vp, _vp, _vp, _vp, ctypes.c_int32, _vp, ctypes.c_int32, _vp,
                                                        _vp, _vp, _vp]),
+    "fetode_driven_grid": (ctypes.c_int, [ctypes.POINTER(FerroDesc), _vp, ctypes.c_int32, _vp, ctypes.c_int64, _vp,
+                                          ctypes.c_int64, ctypes.c_int64, _vp, ctypes.c_int32, _vp, _vp, _vp, _vp]),
+    "fetode_driven_grid_tape": (ctypes.c_int, [ctypes.POINTER(FerroDesc), _vp, ctypes.c_int32, _vp, ctypes.c_int64,
+                                               _vp, ctypes.c_int64, ctypes.c_int64, _vp, ctypes.c_int32, _vp, _vp,
+                                               _vp, _vp, _vp, _vp]),
+    "fetode_driven_grid_backward": (ctypes.c_int, [ctypes.POINTER(FerroDesc), _vp, ctypes.c_int32, ctypes.c_int64,
+                                                   _vp, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "fetode_driven_grid_backward_x": (ctypes.c_int, [ctypes.POINTER(FerroDesc), _vp, ctypes.c_int32, ctypes.c_int64,
+                                                     _vp, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "fetode_driven_table_backward_workspace": (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int64]),
     "fetode_driven_table_backward": (ctypes.c_int, [_vp, ctypes.c_int64, _vp, ctypes.c_int32, _vp, ctypes.c_int64,
                                                     ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _vp,

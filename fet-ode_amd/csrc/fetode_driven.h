@@ -13,6 +13,9 @@ constexpr int kDrvKMax = 16;
 constexpr int kDrvInMax = kDrvHMax + kDrvDMax;
 constexpr int kDrvThreads = 256;  // four waves: lane -> output o, wave -> inputs i = wave (mod 4)
 
+// evaluations per step of the four fixed-grid methods as a shift (1, 2, 4, 4); -1: not a fixed-grid method
+constexpr int drv_nm_log2(int method) { return method == 0 ? 0 : method == 1 ? 1 : (method == 2 || method == 3) ? 2 : -1; }
+
 // Plan (floats): In*K*H elements of 4 constants, element (i, k, o) at ((i*K + k)*H + o)*4 so that
 // the 64 lanes of a wave (o) read consecutive 16-byte words:
 //   .x  gate_slope*log2e*Ec     .y  2*log2e*k     .z  2*log2e*k*Ec     .w  coef*Ps
@@ -24,7 +27,8 @@ struct DrivenArgs {
   const float* plan;
   const float* h0;       // (B, H)
   const float* u;        // (n_eval, B, D) driving table
-  const float* dt;       // (n_steps) fp32 step sizes of the steps this launch takes
+  const float* dt;       // (n_steps) fp32 step sizes of the steps this launch takes; the GRID kernels:
+                         // (n_steps, 4) rows of dt, fp32(dt / 2), fp32(dt / 6), 0 (Schedule.step_coef)
   const float* prev0;    // (B, H+D) hysteresis input before the first evaluation, null: zeros
   float* sol;            // (n_steps, B, H) the state after every step
   float* prev_out;       // (B, H+D) nullable: the last evaluation's input
@@ -34,13 +38,14 @@ struct DrivenArgs {
   int64_t eval0;         // first evaluation (row of u / the tape) of this launch
   int32_t H, D, K, n_steps;
   float gs, gsl2e, wc;   // gate_slope, gate_slope*log2e, -2(1-alpha)
+  int32_t method, nm_log2;   // the GRID kernels only: FETODE_EULER.., log2 of the evaluations per step
 };
 
 struct DrivenAdjArgs {
   const float* plan;
-  const float* dt;        // (n_steps)
+  const float* dt;        // (n_steps); the GRID kernels: (n_steps, 4) as in DrivenArgs
   const float* prev0;     // (B, H+D) nullable
-  const float* tape_hx;   // (4 n_steps, B, H+D)
+  const float* tape_hx;   // (4 n_steps, B, H+D); the GRID kernels: n_m n_steps rows here and below
   const float* tape_phi;  // (4 n_steps, B, H)
   const float* grad_sol;  // (n_steps + 1, B, H): d loss / d every trajectory row, row 0 = h0
   float* adj;             // (4 n_steps, B, H): d loss / d every evaluation's output
@@ -49,6 +54,7 @@ struct DrivenAdjArgs {
   int64_t B;
   int32_t H, D, K, n_steps;
   float gs, gsl2e, wc;
+  int32_t method, nm_log2;   // the GRID kernels only
 };
 
 }  // namespace fetode

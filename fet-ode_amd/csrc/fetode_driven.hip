@@ -4,6 +4,8 @@
 //   driven_table_kernel   x(t) at every evaluation time, the reference's fp32 expression (:861-872)
 //   driven_plan_kernel    per-element constants + sum bias*coef per output, one launch
 //   driven_fixed_kernel   the whole fixed-grid solve; a workgroup owns its samples from h0 to the end
+//                         (GRID: euler, midpoint, rk4 and rk4_classic on a per-step coefficient array,
+//                         the fetode_driven_grid entries)
 //   driven_adj_kernel     the reverse sweep along the chain of evaluations (d/dh; with XG also d/dx(t)
 //                         of every evaluation; the parameter sums over the taped rows:
 //                         fetode_driven_pgrad.hip or the generic Ferro backward)
@@ -151,7 +153,11 @@ __global__ __launch_bounds__(256) void driven_plan_kernel(fetode_ferro_t fl, con
 // ---------------------------------------------------------------------------------------------
 // forward solve
 // ---------------------------------------------------------------------------------------------
-template <int S, int KT, bool TAPE>
+// GRID: the four fixed-grid methods (a.method, uniform per launch) with n_m = 1 << a.nm_log2
+// evaluations per step and the coefficients of step s at a.dt[4 s ..] (dt, fp32(dt / 2), fp32(dt / 6));
+// the combines follow rk_combine_kernel's op order as _per_stage_fixed calls it.  GRID off is the
+// rk4 (3/8) kernel of fetode_driven_fixed: the method folds at compile time.
+template <int S, int KT, bool TAPE, bool GRID = false>
 __global__ __launch_bounds__(kDrvThreads) void driven_fixed_kernel(DrivenArgs a) {
   __shared__ float xs[S][kDrvInMax], gxs[S][kDrvInMax], vs[S][kDrvInMax];
   __shared__ float part[4][S][64];
@@ -195,9 +201,11 @@ __global__ __launch_bounds__(kDrvThreads) void driven_fixed_kernel(DrivenArgs a)
     publish(ds, H + dd, live ? a.u[(a.eval0 * B + b) * D + dd] : 0.f,
             (live && a.prev0) ? a.prev0[b * In + H + dd] : 0.f);
   }
-  const int n_eval = 4 * a.n_steps;
+  const int method = GRID ? a.method : FETODE_RK4;
+  const int sh = GRID ? a.nm_log2 : 2, fin = (1 << sh) - 1;   // a step's last evaluation
+  const int n_eval = a.n_steps << sh;
   for (int e = 0; e < n_eval; ++e) {
-    const int st = e & 3, step = e >> 2;
+    const int st = e & fin, step = e >> sh;   // e % n_m, e / n_m
     const int64_t ge = a.eval0 + e;
     __syncthreads();  // this evaluation's inputs are published
     if (TAPE) {
@@ -241,7 +249,12 @@ __global__ __launch_bounds__(kDrvThreads) void driven_fixed_kernel(DrivenArgs a)
     __syncthreads();  // partial sums are in; nobody reads this evaluation's inputs any more
     const bool last = e == n_eval - 1;
     if (own) {
-      const float dt = a.dt[step];
+      const float dt = a.dt[GRID ? 4 * (int64_t)step : (int64_t)step];
+      float hh = 0.f, h6 = 0.f;
+      if (GRID) {
+        hh = a.dt[4 * (int64_t)step + 1];
+        h6 = a.dt[4 * (int64_t)step + 2];
+      }
 #pragma unroll
       for (int s = 0; s < S; ++s) {
         const int64_t b = b0 + s;
@@ -250,7 +263,21 @@ __global__ __launch_bounds__(kDrvThreads) void driven_fixed_kernel(DrivenArgs a)
         if (TAPE && live) a.tape_phi[(ge * B + b) * H + lane] = phi;
         const float f = tanhf(phi) * gain + bias;
         float xn;  // torchdiffeq rk4_alt_step_func, its op order
-        if (st == 0) {
+        if (GRID && method != FETODE_RK4) {
+          // euler y + dt k1; midpoint y + hh k1 | y + dt k2; classic y + hh k1 | y + hh k2 | y + dt k3 |
+          // y + h6 (((k1 + 2 k2) + 2 k3) + k4)
+          if (st < fin) {
+            if (st == 0) k1[s] = f;
+            else if (st == 1) k2[s] = f;
+            else k3[s] = f;
+            xn = h[s] + (st == 2 ? dt : hh) * f;
+          } else {
+            if (method == FETODE_RK4_CLASSIC) xn = h[s] + h6 * (((k1[s] + 2.0f * k2[s]) + 2.0f * k3[s]) + f);
+            else xn = h[s] + dt * f;
+            h[s] = xn;
+            if (live) a.sol[((int64_t)step * B + b) * H + lane] = xn;
+          }
+        } else if (st == 0) {
           k1[s] = f;
           xn = h[s] + (dt * f) * kThird;
         } else if (st == 1) {
@@ -290,9 +317,10 @@ __device__ __forceinline__ float wave_sum(float v) {
   return v;
 }
 
-// XG: the D driving inputs carry an adjoint too; adj_u (4 n_steps, B, D) receives it per evaluation.
+// XG: the D driving inputs carry an adjoint too; adj_u (one row per evaluation, B, D) receives it.
 // The h inputs' arithmetic is the same either way, so adj and grad_h0 are the same bits.
-template <int S, int KT, bool XG>
+// GRID: as in driven_fixed_kernel; the adjoints of the three other combines are written beside them.
+template <int S, int KT, bool XG, bool GRID = false>
 __global__ __launch_bounds__(kDrvThreads) void driven_adj_kernel(DrivenAdjArgs a) {
   constexpr int NI = XG ? kDrvInMax : kDrvHMax;
   __shared__ float xs[S][NI], gxs[S][NI], vs[S][NI], us[S][NI];
@@ -314,15 +342,37 @@ __global__ __launch_bounds__(kDrvThreads) void driven_adj_kernel(DrivenAdjArgs a
     lam[s] = (own && b < B) ? a.grad_sol[((int64_t)n_steps * B + b) * H + lane] : 0.f;
     ay[s] = ak1[s] = ak2[s] = ak3[s] = ak4[s] = 0.f;
   }
-  for (int e = 4 * n_steps - 1; e >= 0; --e) {
-    const int st = e & 3, step = e >> 2;
-    const float dt = a.dt[step];
+  const int method = GRID ? a.method : FETODE_RK4;
+  const int sh = GRID ? a.nm_log2 : 2, fin = (1 << sh) - 1;
+  const bool alt = GRID && method != FETODE_RK4;
+  for (int e = (n_steps << sh) - 1; e >= 0; --e) {
+    const int st = e & fin, step = e >> sh;
+    const float dt = a.dt[GRID ? 4 * (int64_t)step : (int64_t)step];
+    float hh = 0.f, h6 = 0.f;
+    if (GRID) {
+      hh = a.dt[4 * (int64_t)step + 1];
+      h6 = a.dt[4 * (int64_t)step + 2];
+    }
     if (own) {
 #pragma unroll
       for (int s = 0; s < S; ++s) {
         const int64_t b = b0 + s;
         const bool live = b < B;
-        if (st == 3) {  // y1 = y + ((k1 + 3 (k2 + k3)) + k4) dt / 8
+        if (GRID) {
+          // rk4 as below; classic y1 = y + h6 (((k1 + 2 k2) + 2 k3) + k4); midpoint y1 = y + dt k2; euler
+          // y1 = y + dt k1.  Selects of values under the run-time method (ak3, ak4: read by the 4-stage rules)
+          const bool top = st == fin, cl = method == FETODE_RK4_CLASSIC;
+          const float w8 = (lam[s] * dt) * 0.125f, c6 = h6 * lam[s], cd = dt * lam[s];
+          const float n1 = alt ? (cl ? c6 : (method == FETODE_MIDPOINT ? 0.f : cd)) : w8;
+          const float n2 = alt ? (cl ? 2.0f * c6 : cd) : 3.0f * w8;
+          const float n3 = alt ? 2.0f * c6 : 3.0f * w8;
+          const float n4 = alt ? c6 : w8;
+          ay[s] = top ? lam[s] : ay[s];
+          ak1[s] = top ? n1 : ak1[s];
+          ak2[s] = top ? n2 : ak2[s];
+          ak3[s] = top ? n3 : ak3[s];
+          ak4[s] = top ? n4 : ak4[s];
+        } else if (st == 3) {  // y1 = y + ((k1 + 3 (k2 + k3)) + k4) dt / 8
           ay[s] = lam[s];
           ak1[s] = ak4[s] = (lam[s] * dt) * 0.125f;
           ak2[s] = ak3[s] = 3.0f * ((lam[s] * dt) * 0.125f);
@@ -401,7 +451,21 @@ __global__ __launch_bounds__(kDrvThreads) void driven_adj_kernel(DrivenAdjArgs a
       for (int s = 0; s < S; ++s) {
         const float g = gout[s][lane];
         ay[s] += g;
-        if (st == 3) {         // input y + dt ((k1 - k2) + k3)
+        if (GRID) {
+          // rk4: the three inputs below; the others: input y + c k_st, c = dt at the classic rule's last
+          // stage, else hh.  u_j: this evaluation's input holds k_j with weight c_j (selects of values)
+          const float dt3 = dt * kThird;
+          const float c1 = alt ? hh : (st == 3 ? dt : (st == 2 ? -dt3 : dt3));
+          const float c2 = alt ? hh : (st == 3 ? -dt : dt);
+          const float c3 = dt;
+          const bool u1 = alt ? st == 1 : st >= 1, u2 = alt ? st == 2 : st >= 2, u3 = st == 3;
+          ak1[s] = u1 ? ak1[s] + c1 * g : ak1[s];
+          ak2[s] = u2 ? ak2[s] + c2 * g : ak2[s];
+          ak3[s] = u3 ? ak3[s] + c3 * g : ak3[s];
+          const int64_t b = b0 + s;   // st == 0: input y, the step is done
+          const float gs0 = (st == 0 && b < B) ? a.grad_sol[((int64_t)step * B + b) * H + lane] : 0.f;
+          lam[s] = st == 0 ? ay[s] + gs0 : lam[s];
+        } else if (st == 3) {  // input y + dt ((k1 - k2) + k3)
           ak1[s] += dt * g;
           ak2[s] -= dt * g;
           ak3[s] += dt * g;
@@ -444,32 +508,32 @@ int choose_spw(int64_t B) {
   return B <= 512 ? 1 : (B <= 1024 ? 2 : 4);
 }
 
-template <int S, bool TAPE>
+template <int S, bool TAPE, bool GRID>
 void launch_fixed_s(int K, int64_t grid, hipStream_t st, const DrivenArgs& a) {
   const dim3 g((unsigned)grid), t(kDrvThreads);
-  if (K == 10) hipLaunchKernelGGL((driven_fixed_kernel<S, 10, TAPE>), g, t, 0, st, a);
-  else if (K == 12) hipLaunchKernelGGL((driven_fixed_kernel<S, 12, TAPE>), g, t, 0, st, a);
-  else hipLaunchKernelGGL((driven_fixed_kernel<S, 0, TAPE>), g, t, 0, st, a);
+  if (K == 10) hipLaunchKernelGGL((driven_fixed_kernel<S, 10, TAPE, GRID>), g, t, 0, st, a);
+  else if (K == 12) hipLaunchKernelGGL((driven_fixed_kernel<S, 12, TAPE, GRID>), g, t, 0, st, a);
+  else hipLaunchKernelGGL((driven_fixed_kernel<S, 0, TAPE, GRID>), g, t, 0, st, a);
 }
-template <bool TAPE>
+template <bool TAPE, bool GRID = false>
 void launch_fixed(int spw, int K, int64_t grid, hipStream_t st, const DrivenArgs& a) {
-  if (spw == 1) launch_fixed_s<1, TAPE>(K, grid, st, a);
-  else if (spw == 2) launch_fixed_s<2, TAPE>(K, grid, st, a);
-  else launch_fixed_s<4, TAPE>(K, grid, st, a);
+  if (spw == 1) launch_fixed_s<1, TAPE, GRID>(K, grid, st, a);
+  else if (spw == 2) launch_fixed_s<2, TAPE, GRID>(K, grid, st, a);
+  else launch_fixed_s<4, TAPE, GRID>(K, grid, st, a);
 }
 
-template <int S, bool XG>
+template <int S, bool XG, bool GRID>
 void launch_adj_s(int K, int64_t grid, hipStream_t st, const DrivenAdjArgs& a) {
   const dim3 g((unsigned)grid), t(kDrvThreads);
-  if (K == 10) hipLaunchKernelGGL((driven_adj_kernel<S, 10, XG>), g, t, 0, st, a);
-  else if (K == 12) hipLaunchKernelGGL((driven_adj_kernel<S, 12, XG>), g, t, 0, st, a);
-  else hipLaunchKernelGGL((driven_adj_kernel<S, 0, XG>), g, t, 0, st, a);
+  if (K == 10) hipLaunchKernelGGL((driven_adj_kernel<S, 10, XG, GRID>), g, t, 0, st, a);
+  else if (K == 12) hipLaunchKernelGGL((driven_adj_kernel<S, 12, XG, GRID>), g, t, 0, st, a);
+  else hipLaunchKernelGGL((driven_adj_kernel<S, 0, XG, GRID>), g, t, 0, st, a);
 }
-template <bool XG>
+template <bool XG, bool GRID = false>
 void launch_adj(int spw, int K, int64_t grid, hipStream_t st, const DrivenAdjArgs& a) {
-  if (spw == 1) launch_adj_s<1, XG>(K, grid, st, a);
-  else if (spw == 2) launch_adj_s<2, XG>(K, grid, st, a);
-  else launch_adj_s<4, XG>(K, grid, st, a);
+  if (spw == 1) launch_adj_s<1, XG, GRID>(K, grid, st, a);
+  else if (spw == 2) launch_adj_s<2, XG, GRID>(K, grid, st, a);
+  else launch_adj_s<4, XG, GRID>(K, grid, st, a);
 }
 
 int driven_fixed(const fetode_ferro_t* fl, const void* plan, int32_t method, const float* h0, int64_t B, const float* u,
@@ -522,6 +586,72 @@ int driven_backward(const fetode_ferro_t* basis, const void* plan, int32_t metho
   a.wc = (float)(-2.0 * (1.0 - basis->alpha));
   if (xg) launch_adj<true>(spw, a.K, grid, (hipStream_t)stream, a);
   else launch_adj<false>(spw, a.K, grid, (hipStream_t)stream, a);
+  LAUNCH_CHECK();
+  return FETODE_OK;
+}
+
+// The four fixed-grid methods on a (n_steps, 4) coefficient array; every status is decided before a launch.
+int driven_grid_checks(const fetode_ferro_t* fl, int32_t method, int64_t B, int32_t n_steps, int* spw, int64_t* grid) {
+  if (!drv_shape_ok(fl)) return set_err(FETODE_EUNSUPPORTED, "driven grid: shape outside the admitted family");
+  if (drv_nm_log2(method) < 0)
+    return set_err(FETODE_EUNSUPPORTED, "driven grid: method %d is not euler, midpoint, rk4 or rk4_classic", method);
+  *spw = choose_spw(B > 0 ? B : 1);
+  *grid = B > 0 ? (B + *spw - 1) / *spw : 0;
+  if (*grid > 0x7fffffff || (n_steps > 0 && ((int64_t)n_steps << drv_nm_log2(method)) > 0x7fffffff))
+    return set_err(FETODE_EUNSUPPORTED, "driven grid: batch or evaluation count beyond 2^31 - 1");
+  return FETODE_OK;
+}
+
+int driven_grid(const fetode_ferro_t* fl, const void* plan, int32_t method, const float* h0, int64_t B, const float* u,
+                int64_t n_eval, int64_t eval0, const float* coef, int32_t n_steps, const float* prev0, float* sol,
+                float* prev_out, float* tape_hx, float* tape_phi, bool tape, void* stream) {
+  int spw = 1;
+  int64_t grid = 0;
+  const int rc = driven_grid_checks(fl, method, B, n_steps, &spw, &grid);
+  if (rc != FETODE_OK) return rc;
+  if (B <= 0 || n_steps <= 0) return FETODE_OK;
+  const int sh = drv_nm_log2(method);
+  if (eval0 < 0 || eval0 + ((int64_t)n_steps << sh) > n_eval)
+    return set_err(FETODE_EINVAL, "driven grid: evaluations %lld + %d * %d exceed the table's %lld rows",
+                   (long long)eval0, 1 << sh, n_steps, (long long)n_eval);
+  if (!plan || !h0 || !u || !coef || !sol || (tape && (!tape_hx || !tape_phi)))
+    return set_err(FETODE_EINVAL, "driven grid: null pointer");
+  DrivenArgs a{};
+  a.plan = (const float*)plan;
+  a.h0 = h0; a.u = u; a.dt = coef; a.prev0 = prev0; a.sol = sol; a.prev_out = prev_out;
+  a.tape_hx = tape_hx; a.tape_phi = tape_phi;
+  a.B = B; a.eval0 = eval0;
+  a.H = fl->out_dim; a.D = fl->in_dim - fl->out_dim; a.K = fl->num_basis; a.n_steps = n_steps;
+  a.gs = (float)fl->gate_slope; a.gsl2e = (float)fl->gate_slope * FETODE_LOG2E;
+  a.wc = (float)(-2.0 * (1.0 - fl->alpha));
+  a.method = method; a.nm_log2 = sh;
+  if (tape) launch_fixed<true, true>(spw, a.K, grid, (hipStream_t)stream, a);
+  else launch_fixed<false, true>(spw, a.K, grid, (hipStream_t)stream, a);
+  LAUNCH_CHECK();
+  return FETODE_OK;
+}
+
+int driven_grid_backward(const fetode_ferro_t* basis, const void* plan, int32_t method, int64_t B, const float* coef,
+                         int32_t n_steps, const float* prev0, const float* tape_hx, const float* tape_phi,
+                         const float* grad_sol, float* adj, float* grad_h0, float* adj_u, bool xg, void* stream) {
+  int spw = 1;
+  int64_t grid = 0;
+  const int rc = driven_grid_checks(basis, method, B, n_steps, &spw, &grid);
+  if (rc != FETODE_OK) return rc;
+  if (B <= 0 || n_steps <= 0) return FETODE_OK;
+  if (!plan || !coef || !tape_hx || !tape_phi || !grad_sol || !adj || !grad_h0 || (xg && !adj_u))
+    return set_err(FETODE_EINVAL, "driven grid backward: null pointer");
+  DrivenAdjArgs a{};
+  a.plan = (const float*)plan;
+  a.dt = coef; a.prev0 = prev0; a.tape_hx = tape_hx; a.tape_phi = tape_phi; a.grad_sol = grad_sol;
+  a.adj = adj; a.grad_h0 = grad_h0; a.adj_u = adj_u;
+  a.B = B;
+  a.H = basis->out_dim; a.D = basis->in_dim - basis->out_dim; a.K = basis->num_basis; a.n_steps = n_steps;
+  a.gs = (float)basis->gate_slope; a.gsl2e = (float)basis->gate_slope * FETODE_LOG2E;
+  a.wc = (float)(-2.0 * (1.0 - basis->alpha));
+  a.method = method; a.nm_log2 = drv_nm_log2(method);
+  if (xg) launch_adj<true, true>(spw, a.K, grid, (hipStream_t)stream, a);
+  else launch_adj<false, true>(spw, a.K, grid, (hipStream_t)stream, a);
   LAUNCH_CHECK();
   return FETODE_OK;
 }
@@ -600,6 +730,37 @@ int fetode_driven_fixed_backward_x(const fetode_ferro_t* basis, const void* plan
                                    float* adj_u, void* stream) {
   return driven_backward(basis, plan, method, B, dt, n_steps, prev0, tape_hx, tape_phi, grad_sol, adj, grad_h0, adj_u,
                          true, stream);
+}
+
+int fetode_driven_grid(const fetode_ferro_t* basis, const void* plan, int32_t method, const float* h0, int64_t B,
+                       const float* u, int64_t n_eval, int64_t eval0, const float* coef, int32_t n_steps,
+                       const float* prev0, float* sol, float* prev_out, void* stream) {
+  return driven_grid(basis, plan, method, h0, B, u, n_eval, eval0, coef, n_steps, prev0, sol, prev_out, nullptr,
+                     nullptr, false, stream);
+}
+
+int fetode_driven_grid_tape(const fetode_ferro_t* basis, const void* plan, int32_t method, const float* h0, int64_t B,
+                            const float* u, int64_t n_eval, int64_t eval0, const float* coef, int32_t n_steps,
+                            const float* prev0, float* sol, float* prev_out, float* tape_hx, float* tape_phi,
+                            void* stream) {
+  return driven_grid(basis, plan, method, h0, B, u, n_eval, eval0, coef, n_steps, prev0, sol, prev_out, tape_hx,
+                     tape_phi, true, stream);
+}
+
+int fetode_driven_grid_backward(const fetode_ferro_t* basis, const void* plan, int32_t method, int64_t B,
+                                const float* coef, int32_t n_steps, const float* prev0, const float* tape_hx,
+                                const float* tape_phi, const float* grad_sol, float* adj, float* grad_h0,
+                                void* stream) {
+  return driven_grid_backward(basis, plan, method, B, coef, n_steps, prev0, tape_hx, tape_phi, grad_sol, adj, grad_h0,
+                              nullptr, false, stream);
+}
+
+int fetode_driven_grid_backward_x(const fetode_ferro_t* basis, const void* plan, int32_t method, int64_t B,
+                                  const float* coef, int32_t n_steps, const float* prev0, const float* tape_hx,
+                                  const float* tape_phi, const float* grad_sol, float* adj, float* grad_h0,
+                                  float* adj_u, void* stream) {
+  return driven_grid_backward(basis, plan, method, B, coef, n_steps, prev0, tape_hx, tape_phi, grad_sol, adj, grad_h0,
+                              adj_u, true, stream);
 }
 
 int64_t fetode_driven_table_backward_workspace(int64_t B, int64_t n_ev) {

@@ -27,9 +27,11 @@ FETODE_ECG_DOPRI5_TAPE=1) a No_MLP_KANODEFunc training solve is the device-resid
 """
 from __future__ import annotations
 
+import math
 from types import SimpleNamespace
 from typing import Optional
 
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -422,6 +424,8 @@ _DRIVEN_DOPRI5_TRAIN = [_lib.os.environ.get("FETODE_DRIVEN_DOPRI5_TRAIN", "0") =
 _DRIVEN_TAPE_ATTEMPTS = 64   # attempts per sample the first taped launch has room for
 _DRIVEN_PARAM_GRADS = [_lib.os.environ.get("FETODE_DRIVEN_PARAM_GRADS", "0") == "1"]
 _DRIVEN_XGRAD = [_lib.os.environ.get("FETODE_DRIVEN_XGRAD", "0") == "1"]
+_DRIVEN_METHODS = [_lib.os.environ.get("FETODE_DRIVEN_METHODS", "0") == "1"]
+_GRID_STAGES = {_lib.EULER: 1, _lib.MIDPOINT: 2, _lib.RK4: 4, _lib.RK4_CLASSIC: 4}   # evaluations per step
 
 
 def set_fused_driven(enabled: bool) -> bool:
@@ -637,15 +641,10 @@ def _driven_rules(func, t, tc, reversed_) -> bool:
     return bool(_lib.load().fetode_driven_supported(_lib.ctypes.byref(func.basis.desc(keep))))
 
 
-def driven_recognise(func, y0, t, tc, step_size, reversed_, method_code):
-    """(x (B, T, D), grid tensors) of a solve the fused driven path reproduces, or None:
-    driven_eligible, and every tensor fp32 on y0's GPU with matching shapes; a driving series that
-    requires grad is left to the per-stage path unless set_driven_series_grad is on, and is then
-    returned attached (a 2-D series as its expand over the batch, so autograd sums the rows)."""
-    if y0.dim() != 2 or y0.dtype != torch.float32 or not y0.is_cuda:
-        return None
-    if not driven_eligible(func, t, tc, step_size, reversed_, method_code):
-        return None
+def _driven_series(func, y0):
+    """The driving series (B, T, D) of an eligible solve, or None: every tensor fp32 on y0's GPU with
+    matching shapes; detached and contiguous unless it requires grad and set_driven_series_grad is on
+    (then attached; a 2-D series as its expand over the batch, so autograd sums the rows)."""
     x, tg = func._interp.x, func._interp.t
     B, H = y0.shape
     if x.dim() == 2:
@@ -659,7 +658,20 @@ def driven_recognise(func, y0, t, tc, step_size, reversed_, method_code):
         return None
     if any(p.device != y0.device or p.dtype != torch.float32 for p in _driven_tensors(func)):
         return None
-    return (x if xgrad else x.detach().contiguous()), _driven_grid(tc, y0.device)
+    return x if xgrad else x.detach().contiguous()
+
+
+def driven_recognise(func, y0, t, tc, step_size, reversed_, method_code):
+    """(x (B, T, D), grid tensors) of a solve the fused driven path reproduces, or None:
+    driven_eligible, and every tensor fp32 on y0's GPU with matching shapes; a driving series that
+    requires grad is left to the per-stage path unless set_driven_series_grad is on, and is then
+    returned attached (a 2-D series as its expand over the batch, so autograd sums the rows)."""
+    if y0.dim() != 2 or y0.dtype != torch.float32 or not y0.is_cuda:
+        return None
+    if not driven_eligible(func, t, tc, step_size, reversed_, method_code):
+        return None
+    x = _driven_series(func, y0)
+    return None if x is None else (x, _driven_grid(tc, y0.device))
 
 
 def _driven_prev0(f, h0, u):
@@ -804,10 +816,11 @@ class _DrivenFn(torch.autograd.Function):
 
 
 def driven_solve(func, y0, t, tc, step_size, reversed_, method_code):
-    """odeint's hook: the fused solve of a recognised input-driven field (T, B, H), or None."""
+    """odeint's hook: the fused solve of a recognised input-driven field (T, B, H), or None.  Plain rk4
+    first; then, with set_fused_driven_methods on, the other fixed-grid configurations."""
     rec = driven_recognise(func, y0, t, tc, step_size, reversed_, method_code)
     if rec is None:
-        return None
+        return driven_grid_solve(func, y0, t, tc, step_size, reversed_, method_code) if _DRIVEN_METHODS[0] else None
     x, grids = rec
     ent = _driven_plan(func, y0.device)
     if ent is None:
@@ -819,6 +832,206 @@ def driven_solve(func, y0, t, tc, step_size, reversed_, method_code):
     h0 = _lib.f32c(y0)
     u = driven_table(grids[0], x, grids[1])
     return _driven_launch(func, plan, d, h0, u, grids[2], _driven_prev0(func, h0, u), grids[2].numel(), False)[0]
+
+
+# ---------------------------------------------------------------------------------------------
+# euler, midpoint, rk4_classic and the step_size option in one launch
+# ---------------------------------------------------------------------------------------------
+# Behind set_fused_driven_methods (off by default): the solves driven_eligible declines — another
+# fixed-grid method, or a step_size — run through fetode_driven_grid* on odeint's own Schedule: one
+# launch over the schedule's steps, the stage times of every step in _per_stage_fixed's expressions,
+# and the (T, B, H) result picked from the per-step states by the schedule's out_step / out_mode /
+# out_slope in ordinary torch ops, so autograd hands the sweep its per-step grad_sol.
+
+def set_fused_driven_methods(enabled: bool) -> bool:
+    """Solve input-driven fields under euler, midpoint, rk4_classic, or any of the four fixed-grid
+    methods with a step_size, in one launch (fetode_driven_grid*) instead of stage by
+    stage (default off; env FETODE_DRIVEN_METHODS=1 turns it on).  Plain rk4 without a step_size keeps
+    its own path either way.  Returns the previous value."""
+    prev, _DRIVEN_METHODS[0] = _DRIVEN_METHODS[0], bool(enabled)
+    return prev
+
+
+def _step_size_ok(step_size) -> bool:
+    if step_size is None:
+        return True
+    if isinstance(step_size, bool) or not isinstance(step_size, (int, float)):
+        return False
+    return math.isfinite(step_size) and step_size > 0
+
+
+def driven_grid_eligible(func, t, tc, step_size, reversed_, method_code) -> bool:
+    """The rules of the one-launch solve of the other fixed-grid configurations that need no GPU:
+    both knobs on, _driven_rules, one of the four fixed-grid methods, step_size None or a positive
+    finite number — and not plain rk4 without a step_size, which is driven_eligible's."""
+    if not (_FUSED_DRIVEN and _DRIVEN_METHODS[0]) or method_code not in _GRID_STAGES:
+        return False
+    if not _step_size_ok(step_size) or (method_code == _lib.RK4 and step_size is None):
+        return False
+    return _driven_rules(func, t, tc, reversed_)
+
+
+def driven_stage_times(grid, method_code):
+    """The evaluation times of every step of `grid` (numpy, the time dtype) in call order, n_m per
+    step: _per_stage_fixed's expressions for euler, midpoint and rk4_classic, _driven_grid's (torchdiffeq's
+    rk4_alt_step_func) for rk4.  A CPU tensor in the grid's dtype."""
+    t0, t1 = grid[:-1], grid[1:]
+    if method_code == _lib.RK4:
+        a, b = torch.from_numpy(t0.copy()), torch.from_numpy(t1.copy())
+        dt = b - a
+        return torch.stack([a, a + dt * (1 / 3), a + dt * (2 / 3), b], dim=1).reshape(-1)
+    if method_code == _lib.EULER:
+        cols = [t0]
+    elif method_code == _lib.MIDPOINT:
+        cols = [t0, t0 + 0.5 * (t1 - t0)]
+    else:
+        hs = t1 - t0
+        cols = [t0, t0 + 0.5 * hs, t0 + 0.5 * hs, t0 + hs]
+    return torch.from_numpy(np.stack(cols, axis=1).reshape(-1).astype(grid.dtype, copy=False).copy())
+
+
+def driven_grid_selection(sched, dev):
+    """What driven_grid_outputs needs of a schedule, on dev: (out_step, out_step + 1, out_mode (T, 1, 1),
+    out_slope (T, 1, 1)) — or None where output j is the state after step j - 1 (no step_size)."""
+    n, T = sched.n_steps, sched.T
+    if n == T - 1 and bool((sched.out_mode[1:] == 1).all()) and bool((sched.out_step[1:] == np.arange(T - 1)).all()):
+        return None
+    i0 = torch.from_numpy(sched.out_step.astype(np.int64))
+    return (i0.to(dev), (i0 + 1).to(dev), torch.from_numpy(sched.out_mode.astype(np.int64)).view(T, 1, 1).to(dev),
+            torch.from_numpy(sched.out_slope.copy()).view(T, 1, 1).to(dev))
+
+
+def driven_grid_outputs(sol_all, sel):
+    """The (T, B, H) result from the states after every step sol_all (n_steps + 1, B, H; row 0 = y0), in
+    _per_stage_fixed's expression: mode 0 -> y, 1 -> y1, 2 -> y + slope (y1 - y) of step out_step[j]."""
+    i0, i1, mode, slope = sel
+    y, y1 = sol_all.index_select(0, i0), sol_all.index_select(0, i1)
+    return torch.where(mode == 0, y, torch.where(mode == 1, y1, y + slope * (y1 - y)))
+
+
+def _driven_grid_arrays(sched, method_code, dev):
+    """Per (schedule, method, device), uploaded once: the stage times, the (n_steps, 4) coefficients and
+    the output selection (None where every output is the state after its own step)."""
+    key = ("driven", method_code, dev)
+    ent = sched.dev.get(key)
+    if ent is None:
+        tq = driven_stage_times(sched.grid, method_code).to(torch.float32).to(dev)
+        ent = sched.dev[key] = (tq, sched.device_arrays(dev)[1], driven_grid_selection(sched, dev))
+    return ent
+
+
+def driven_grid_recognise(func, y0, t, tc, step_size, reversed_, method_code):
+    """(x (B, T, D), t_grid on y0's GPU) of a solve the grid path reproduces, or None:
+    driven_grid_eligible and driven_recognise's tensor rules (a driving series that requires grad needs
+    set_driven_series_grad)."""
+    if y0.dim() != 2 or y0.dtype != torch.float32 or not y0.is_cuda:
+        return None
+    if not driven_grid_eligible(func, t, tc, step_size, reversed_, method_code):
+        return None
+    x = _driven_series(func, y0)
+    return None if x is None else (x, _driven_grid(tc, y0.device)[0])
+
+
+def _driven_grid_launch(f, plan, d, method_code, h0, u, coef, prev0, n_steps, tape):
+    lib = _lib.load()
+    dev = h0.device
+    B, H = h0.shape
+    In = f.basis.in_dim
+    ne = n_steps * _GRID_STAGES[method_code]
+    sol = torch.empty(n_steps + 1, B, H, device=dev, dtype=torch.float32)
+    sol[0] = h0
+    prev_out = torch.empty(B, In, device=dev, dtype=torch.float32)
+    args = [_lib.ctypes.byref(d), plan.data_ptr(), method_code, h0.data_ptr(), B, u.data_ptr(), u.shape[0], 0,
+            coef.data_ptr(), n_steps, prev0.data_ptr(), sol[1:].data_ptr(), prev_out.data_ptr()]
+    if tape:
+        thx = torch.empty(ne, B, In, device=dev, dtype=torch.float32)
+        tphi = torch.empty(ne, B, H, device=dev, dtype=torch.float32)
+        _lib.check(lib.fetode_driven_grid_tape(*args, thx.data_ptr(), tphi.data_ptr(), _lib.stream_handle(dev)),
+                   "fetode_driven_grid_tape")
+    else:
+        thx = tphi = None
+        _lib.check(lib.fetode_driven_grid(*args, _lib.stream_handle(dev)), "fetode_driven_grid")
+    f.basis._prev = prev_out   # prev_x <- the last evaluation's input (ferro_class.py:409)
+    return sol, thx, tphi
+
+
+class _DrivenGridFn(torch.autograd.Function):
+    """_DrivenFn for the four fixed-grid methods on a schedule's grid: the taped launch over every step
+    (sol: the state after every step, row 0 = h0), one reverse sweep, the parameter sums over the
+    n_m n_steps taped rows and, where the series requires grad, driven_series_grad over the stage times."""
+
+    @staticmethod
+    def forward(ctx, f, x, tg, tq, coef, method_code, n_steps, h0, *params):
+        dev = h0.device
+        plan, d, keep = _driven_plan(f, dev)
+        h0c = _lib.f32c(h0)
+        u = driven_table(tg, _lib.f32c(x), tq)
+        prev0 = _driven_prev0(f, h0c, u)
+        sol, thx, tphi = _driven_grid_launch(f, plan, d, method_code, h0c, u, coef, prev0, n_steps, True)
+        ctx.f, ctx.plan, ctx.d, ctx.keep, ctx.n_steps, ctx.method = f, plan, d, keep, n_steps, method_code
+        ctx.save_for_backward(tg, tq, coef, prev0, thx, tphi, *[p.detach() for p in params])
+        return sol
+
+    @staticmethod
+    def backward(ctx, grad):
+        lib = _lib.load()
+        tg, tq, coef, prev0, thx, tphi, *params = ctx.saved_tensors
+        f, n_steps = ctx.f, ctx.n_steps
+        dev = grad.device
+        g = _lib.f32c(grad)
+        ne, B, H = tphi.shape
+        In = thx.shape[2]
+        adj = torch.empty_like(tphi)
+        gh0 = torch.empty(B, H, device=dev, dtype=torch.float32)
+        args = [_lib.ctypes.byref(ctx.d), ctx.plan.data_ptr(), ctx.method, B, coef.data_ptr(), n_steps,
+                prev0.data_ptr(), thx.data_ptr(), tphi.data_ptr(), g.data_ptr(), adj.data_ptr(), gh0.data_ptr()]
+        gx = None
+        if ctx.needs_input_grad[1]:
+            D = In - H
+            adj_u = torch.empty(ne, B, D, device=dev, dtype=torch.float32)
+            _lib.check(lib.fetode_driven_grid_backward_x(*args, adj_u.data_ptr(), _lib.stream_handle(dev)),
+                       "fetode_driven_grid_backward_x")
+            gx = driven_series_grad(tq, 0, tg, adj_u, B, ne, 1, B, None, 0, D)
+        else:
+            _lib.check(lib.fetode_driven_grid_backward(*args, _lib.stream_handle(dev)), "fetode_driven_grid_backward")
+        want = ctx.needs_input_grad[8:]
+        grads = [None] * 7
+        if any(want) and ne and _DRIVEN_PARAM_GRADS[0]:
+            grads = driven_param_grads(ctx.d, [_lib.f32c(p) for p in params], want, B, ne, 1, B, None, 0, prev0,
+                                       thx, tphi, adj)
+        elif any(want) and ne:
+            grads = _driven_param_sums_generic(f, params[5], want, thx, tphi, adj,
+                                               lambda: torch.cat([prev0.unsqueeze(0), thx[:-1]], dim=0))
+        elif any(want):
+            grads = [torch.zeros_like(p) if w else None for p, w in zip(params, want)]
+        return (None, gx, None, None, None, None, None, gh0 if ctx.needs_input_grad[7] else None, *grads)
+
+
+def driven_grid_solve(func, y0, t, tc, step_size, reversed_, method_code):
+    """driven_solve's second leg: the fused solve (T, B, H) of a recognised input-driven field under
+    euler / midpoint / rk4_classic or a step_size, or None."""
+    rec = driven_grid_recognise(func, y0, t, tc, step_size, reversed_, method_code)
+    if rec is None:
+        return None
+    x, tg = rec
+    dev = y0.device
+    ent = _driven_plan(func, dev)
+    if ent is None:
+        return None
+    from .odeint import get_schedule
+    sched = get_schedule(tc, step_size, False)
+    tq, coef, sel = _driven_grid_arrays(sched, method_code, dev)
+    n_steps = sched.n_steps
+    params = _driven_tensors(func)
+    if torch.is_grad_enabled() and (x.requires_grad or y0.requires_grad or any(p.requires_grad for p in params)):
+        sol_all = _DrivenGridFn.apply(func, x, tg, tq, coef, method_code, n_steps, y0, *params)
+    else:
+        plan, d, _ = ent
+        h0 = _lib.f32c(y0)
+        u = driven_table(tg, x, tq)
+        sol_all = _driven_grid_launch(func, plan, d, method_code, h0, u, coef, _driven_prev0(func, h0, u), n_steps,
+                                      False)[0]
+    return sol_all if sel is None else driven_grid_outputs(sol_all, sel)
 
 
 def driven_dopri5_eligible(func, t, tc, reversed_, rtol, atol, options) -> bool:
@@ -1141,6 +1354,7 @@ class OneODEEncoder(CacheFreeState, nn.Module):
         self.lift = nn.Linear(input_size, hidden_size)
         self.odefunc = InputDrivenKANODEFunc(input_size, hidden_size, num_basis)
         self.last_solve = None
+        self.solver_options = None   # odeint's options= (e.g. {"step_size": h}); not part of the state_dict
 
     def _solve_dopri5(self, xb, t_grid):
         """The whole batch under dopri5 in one launch, a step controller per sample, when the solve is the
@@ -1180,7 +1394,8 @@ class OneODEEncoder(CacheFreeState, nn.Module):
             # every row starts from the reset state (the reference solves it alone, after a reset)
             basis._prev = torch.zeros(xb.size(0), basis.in_dim, device=xb.device, dtype=xb.dtype)
         h0 = self.lift(xb[:, 0])
-        return odeint(self.odefunc, h0, t_grid, method=self.solver, rtol=self.rtol, atol=self.atol)
+        return odeint(self.odefunc, h0, t_grid, method=self.solver, rtol=self.rtol, atol=self.atol,
+                      options=self.solver_options)
 
     def forward(self, xb, return_traj=None):
         assert xb.dim() == 3

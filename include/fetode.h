@@ -784,8 +784,9 @@ int fetode_logistic_basis_backward(const float* x, int64_t B, int32_t in, int32_
  * solved over a whole batch in one launch; every sample carries its own driving signal x(t) and its
  * own hysteresis input (the reference resets the state before each sample's solve).  Admitted
  * family: out_dim = H in 1..64, in_dim - out_dim = D in 1..4, num_basis in 1..16, constant
- * branch_sign (NULL), method FETODE_RK4 (the other methods: FETODE_EUNSUPPORTED), any number of
- * steps.  fetode_driven_supported is a host-only query of that family (1 / 0). */
+ * branch_sign (NULL), method FETODE_RK4 (the other methods: FETODE_EUNSUPPORTED here; the
+ * fetode_driven_grid entries below take the four fixed-grid methods), any number of steps.
+ * fetode_driven_supported is a host-only query of that family (1 / 0). */
 int fetode_driven_supported(const fetode_ferro_t* basis);
 /* Samples per workgroup of the driven kernels: 0 = by batch size (1 up to B = 512, 2 up to 1024, 4
  * beyond), or 1 / 2 / 4 forced; any other argument changes nothing (so a negative one is a query).
@@ -832,6 +833,42 @@ int fetode_driven_fixed_backward_x(const fetode_ferro_t* basis, const void* plan
                                    const float* dt, int32_t n_steps, const float* prev0, const float* tape_hx,
                                    const float* tape_phi, const float* grad_sol, float* adj, float* grad_h0,
                                    float* adj_u, void* stream);
+/* The same one-launch solve for the four fixed-grid methods: FETODE_EULER, FETODE_MIDPOINT, FETODE_RK4
+ * (3/8 rule) and FETODE_RK4_CLASSIC, with n_m = 1, 2, 4, 4 evaluations per step.  coef (n_steps, 4) holds
+ * per step dt, fp32(dt / 2), fp32(dt / 6) and a spare float (odeint's Schedule.step_coef); evaluation e of
+ * the launch reads row eval0 + e of u, so the table holds the method's stage times in call order.  The
+ * combines follow fetode_rk_combine's op order as the per-stage path calls it:
+ *   euler        y1 = y + dt k1
+ *   midpoint     k2 = f(y + hh k1),  y1 = y + dt k2
+ *   rk4_classic  inputs y + hh k1, y + hh k2, y + dt k3;  y1 = y + h6 (((k1 + 2 k2) + 2 k3) + k4)
+ * and every evaluation moves prev <- its input.  sol (n_steps, B, H) receives the state after every step
+ * (output selection between steps is the caller's), prev_out (nullable) the last evaluation's input.
+ * With FETODE_RK4 the results are bitwise fetode_driven_fixed's on the same dt.  Decided before any
+ * launch: FETODE_EUNSUPPORTED for a shape outside fetode_driven_supported, any other method, or more
+ * than 2^31 - 1 workgroups or evaluations; then FETODE_OK without a launch for B <= 0 or n_steps <= 0;
+ * then FETODE_EINVAL for eval0 < 0 or n_eval < eval0 + n_m n_steps, or a NULL plan, h0, u, coef, sol
+ * (or tape). */
+int fetode_driven_grid(const fetode_ferro_t* basis, const void* plan, int32_t method, const float* h0, int64_t B,
+                       const float* u, int64_t n_eval, int64_t eval0, const float* coef, int32_t n_steps,
+                       const float* prev0, float* sol, float* prev_out, void* stream);
+/* The same solve, recording tape_hx (n_eval, B, H + D) and tape_phi (n_eval, B, H) at row eval0 + e. */
+int fetode_driven_grid_tape(const fetode_ferro_t* basis, const void* plan, int32_t method, const float* h0, int64_t B,
+                            const float* u, int64_t n_eval, int64_t eval0, const float* coef, int32_t n_steps,
+                            const float* prev0, float* sol, float* prev_out, float* tape_hx, float* tape_phi,
+                            void* stream);
+/* Reverse sweep of a taped fetode_driven_grid_tape solve that started at evaluation 0, as
+ * fetode_driven_fixed_backward: grad_sol (n_steps + 1, B, H), adj (n_m n_steps, B, H), grad_h0 (B, H);
+ * the tapes hold n_m n_steps rows.  The _x entry also writes adj_u (n_m n_steps, B, D); adj and grad_h0
+ * are the same bits either way.  With FETODE_RK4: bitwise fetode_driven_fixed_backward(_x).  Statuses as
+ * fetode_driven_grid (FETODE_EINVAL: a NULL pointer other than prev0). */
+int fetode_driven_grid_backward(const fetode_ferro_t* basis, const void* plan, int32_t method, int64_t B,
+                                const float* coef, int32_t n_steps, const float* prev0, const float* tape_hx,
+                                const float* tape_phi, const float* grad_sol, float* adj, float* grad_h0,
+                                void* stream);
+int fetode_driven_grid_backward_x(const fetode_ferro_t* basis, const void* plan, int32_t method, int64_t B,
+                                  const float* coef, int32_t n_steps, const float* prev0, const float* tape_hx,
+                                  const float* tape_phi, const float* grad_sol, float* adj, float* grad_h0,
+                                  float* adj_u, void* stream);
 /* LinearInterp1D's backward: grad_x (B, T, D) = d loss / d the driving series from adj_u = d loss / d
  * every evaluation's x(t).  Row (b, e), b < B, e < n_ev, of adj_u (D floats wide) sits at row index
  * b * stride_b + e * stride_e and its time at tq[b * tq_stride_b + e]: the rk4 sweep's adj_u
