@@ -1,8 +1,11 @@
 // fetode_driven.h — the input-driven Ferro field of the ECG NODE-RNN encoder
 // (compare_noise_ecg.py:875-907):   dh/dt = tanh(Ferro_{(H+D)->H}(cat[h, x(t)])) * gain + bias.
-// Plan layout and launch arguments shared by the kernels of fetode_driven.hip.
+// Plan layout, launch arguments and the host's dispatch helpers shared by the driven kernel files
+// (the device arithmetic: fetode_driven_dev.h).
 #pragma once
 #include <stdint.h>
+
+#include "fetode_common.h"
 
 namespace fetode {
 
@@ -56,5 +59,35 @@ struct DrivenAdjArgs {
   float gs, gsl2e, wc;
   int32_t method, nm_log2;   // the GRID kernels only
 };
+
+// The field constants every driven argument struct carries (H, D, K, gs, gsl2e, wc), from the basis.
+template <class Args>
+inline void drv_fill_field(Args& a, const fetode_ferro_t* fl) {
+  a.H = fl->out_dim;
+  a.D = fl->in_dim - fl->out_dim;
+  a.K = fl->num_basis;
+  a.gs = (float)fl->gate_slope;
+  a.gsl2e = (float)fl->gate_slope * FETODE_LOG2E;
+  a.wc = (float)(-2.0 * (1.0 - fl->alpha));
+}
+
+// Dispatch (the named tables of DESIGN §4.16): a row holds a kernel's three K instantiations, K = 10 and
+// K = 12 at compile time and the run-time K; rows per samples-per-workgroup S = 1, 2, 4 make a DrvSRows.
+// A new driven kernel builds its row(s) where it is defined and launches through drv_launch.
+template <class... A>
+struct DrvKRow {
+  void (*k10)(A...);
+  void (*k12)(A...);
+  void (*kany)(A...);
+};
+template <class... A>
+struct DrvSRows {
+  DrvKRow<A...> s1, s2, s4;
+  const DrvKRow<A...>& at(int spw) const { return spw == 1 ? s1 : (spw == 2 ? s2 : s4); }
+};
+template <class... A>
+inline void drv_launch(const DrvKRow<A...>& r, int K, dim3 grid, int threads, hipStream_t st, const A&... a) {
+  hipLaunchKernelGGL(K == 10 ? r.k10 : (K == 12 ? r.k12 : r.kany), grid, dim3(threads), 0, st, a...);
+}
 
 }  // namespace fetode

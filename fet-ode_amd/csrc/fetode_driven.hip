@@ -16,9 +16,10 @@
 //     m = 1 - 2(1-alpha)(1-u) sigma(gs(-x-Ec)),   u = sigma(gs(x - prev))       (DESIGN §3 "Algebra").
 // Mapping: 256 threads = 4 waves; lane -> output o (lanes >= H idle), wave w -> inputs i = w (mod 4).
 // Every lane sums the K bases of one input first, then its inputs; the four waves'
-// partial sums meet in LDS in a fixed order.  No workgroup waits on another one.
-#include "fetode_common.h"
-#include "fetode_driven.h"
+// partial sums meet in LDS in a fixed order.  No workgroup waits on another one.  The gate, the element
+// loop, the meeting, the VJP and the interpolator's locate step are fetode_driven_dev.h's functions, shared
+// with the dopri5 kernels; the kernels here hold the solver around them.
+#include "fetode_driven_dev.h"
 
 using namespace fetode;
 
@@ -38,14 +39,9 @@ __global__ __launch_bounds__(256) void driven_table_kernel(const float* __restri
     const int d = (int)(idx % D);
     const int64_t b = (idx / D) % B, e = idx / ((int64_t)D * B);
     const float lo = tg[0], hi = tg[T - 1];
-    float t = tq[e];
-    t = t < lo ? lo : (t > hi ? hi : t);                 // torch.clamp(t, t[0], t[-1])
-    int i = 0;                                           // searchsorted, left: #{grid < t}
-    for (int j = 0; j < T; ++j) i += tg[j] < t ? 1 : 0;
-    i = i < 1 ? 1 : (i > T - 1 ? T - 1 : i);             // .clamp(1, T - 1)
-    const float t0 = tg[i - 1], t1 = tg[i];
+    float w;
+    const int i = drv_locate(tg, T, lo, hi, tq[e], w);
     const float x0 = x[(b * T + (i - 1)) * D + d], x1 = x[(b * T + i) * D + d];
-    const float w = (t - t0) / ((t1 - t0) + 1e-12f);
     u[idx] = (1.0f - w) * x0 + w * x1;
   }
 }
@@ -67,8 +63,8 @@ struct DrivenTbArgs {
 };
 
 // Workgroup (b, chunk of 256 outputs): thread -> output (j, d) of sample b.  The sample's evaluations
-// are taken 256 at a time: every thread locates one of them in the grid (driven_table_kernel's fp32
-// expression: clamp, searchsorted left, clamp(1, T - 1), w from the clamped t) into LDS, then every
+// are taken 256 at a time: every thread locates one of them in the grid (drv_locate, the forward's fp32
+// expression) into LDS, then every
 // thread walks the 256 (interval, weight) pairs in order and adds the ones that name its knot.  The
 // order is ascending e whatever the strides are: the same bits for the same rows in either layout.
 __global__ __launch_bounds__(kTbThreads) void driven_table_bwd_kernel(DrivenTbArgs a) {
@@ -90,14 +86,9 @@ __global__ __launch_bounds__(kTbThreads) void driven_table_bwd_kernel(DrivenTbAr
   for (int64_t e0 = 0; e0 < nl; e0 += kTbThreads) {   // nl is uniform: every thread reaches every barrier
     const int64_t e = e0 + tid;
     if (e < nl) {
-      float t = a.tq[b * a.tq_stride_b + e];
-      t = t < lo ? lo : (t > hi ? hi : t);
-      int i = 0;
-      for (int q = 0; q < T; ++q) i += tg[q] < t ? 1 : 0;
-      i = i < 1 ? 1 : (i > T - 1 ? T - 1 : i);
-      const float t0 = tg[i - 1], t1 = tg[i];
-      si[tid] = i;
-      sw[tid] = (t - t0) / ((t1 - t0) + 1e-12f);
+      float w;
+      si[tid] = drv_locate(tg, T, lo, hi, a.tq[b * a.tq_stride_b + e], w);
+      sw[tid] = w;
     }
     __syncthreads();
     const int n = nl - e0 < kTbThreads ? (int)(nl - e0) : kTbThreads;
@@ -179,10 +170,10 @@ __global__ __launch_bounds__(kDrvThreads) void driven_fixed_kernel(DrivenArgs a)
   // input i of sample s for the next evaluation: value, its gate against the previous evaluation's
   // input (prev <- hx, call order) and the per-input factors of the element loop
   auto publish = [&](int s, int i, float xn, float xo) {
-    const float up = 1.0f / (1.0f + expf(-(gs * (xn - xo))));
-    xs[s][i] = xn;
-    gxs[s][i] = gsl2e * xn;
-    vs[s][i] = wc * (1.0f - up);
+    const DrvGate g = drv_gate(gs, gsl2e, wc, xn, xo);
+    xs[s][i] = g.x;
+    gxs[s][i] = g.gx;
+    vs[s][i] = g.v;
   };
   float h[S], k1[S], k2[S], k3[S];
 #pragma unroll
@@ -215,35 +206,7 @@ __global__ __launch_bounds__(kDrvThreads) void driven_fixed_kernel(DrivenArgs a)
       }
     }
     float acc[S];
-#pragma unroll
-    for (int s = 0; s < S; ++s) acc[s] = 0.f;
-    if (lane < H) {
-      for (int i = wv; i < In; i += 4) {
-        float x[S], gx[S], v[S], ai[S];
-#pragma unroll
-        for (int s = 0; s < S; ++s) {
-          x[s] = xs[s][i];
-          gx[s] = gxs[s][i];
-          v[s] = vs[s][i];
-          ai[s] = 0.f;
-        }
-        const float4* __restrict__ p = el + (int64_t)i * K * H + lane;
-#pragma unroll KT > 0 ? KT : 1
-        for (int k = 0; k < K; ++k) {
-          const float4 c = p[(int64_t)k * H];
-#pragma unroll
-          for (int s = 0; s < S; ++s) {
-            const float cn = rcp(1.0f + ex2(gx[s] + c.x));         // sigma(gs(-x - Ec))
-            const float m = ffma(v[s], cn, 1.0f);
-            const float z = ffma(c.z, m, c.y * x[s]);              // 2 log2e k (x + Ec m)
-            const float th = ffma(rcp(1.0f + ex2(z)), -2.0f, 1.0f);  // tanh(k (x + Ec m))
-            ai[s] = ffma(c.w, th, ai[s]);
-          }
-        }
-#pragma unroll
-        for (int s = 0; s < S; ++s) acc[s] += ai[s];
-      }
-    }
+    drv_eval_partial<S, KT>(el, H, In, K, lane, wv, xs, gxs, vs, acc);
 #pragma unroll
     for (int s = 0; s < S; ++s) part[wv][s][lane] = acc[s];
     __syncthreads();  // partial sums are in; nobody reads this evaluation's inputs any more
@@ -259,7 +222,7 @@ __global__ __launch_bounds__(kDrvThreads) void driven_fixed_kernel(DrivenArgs a)
       for (int s = 0; s < S; ++s) {
         const int64_t b = b0 + s;
         const bool live = b < B;
-        const float phi = ((part[0][s][lane] + part[1][s][lane]) + (part[2][s][lane] + part[3][s][lane])) + fcon;
+        const float phi = drv_eval_meet<S>(part, s, lane, fcon);
         if (TAPE && live) a.tape_phi[(ge * B + b) * H + lane] = phi;
         const float f = tanhf(phi) * gain + bias;
         float xn;  // torchdiffeq rk4_alt_step_func, its op order
@@ -311,12 +274,6 @@ __global__ __launch_bounds__(kDrvThreads) void driven_fixed_kernel(DrivenArgs a)
 // ---------------------------------------------------------------------------------------------
 // reverse sweep: adjoints of every evaluation's output and of h0; the gate reads prev detached
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
-
 // XG: the D driving inputs carry an adjoint too; adj_u (one row per evaluation, B, D) receives it.
 // The h inputs' arithmetic is the same either way, so adj and grad_h0 are the same bits.
 // GRID: as in driven_fixed_kernel; the adjoints of the three other combines are written beside them.
@@ -401,11 +358,11 @@ __global__ __launch_bounds__(kDrvThreads) void driven_adj_kernel(DrivenAdjArgs a
         xv = a.tape_hx[((int64_t)e * B + b) * In + i];
         pv = e > 0 ? a.tape_hx[((int64_t)(e - 1) * B + b) * In + i] : (a.prev0 ? a.prev0[b * In + i] : 0.f);
       }
-      const float up = 1.0f / (1.0f + expf(-(gs * (xv - pv))));
-      xs[s][i] = xv;
-      gxs[s][i] = gsl2e * xv;
-      vs[s][i] = wc * (1.0f - up);
-      us[s][i] = up;
+      const DrvGate g = drv_gate(gs, gsl2e, wc, xv, pv);
+      xs[s][i] = g.x;
+      gxs[s][i] = g.gx;
+      vs[s][i] = g.v;
+      us[s][i] = g.u;
     }
     __syncthreads();
     float gp[S];
@@ -421,16 +378,7 @@ __global__ __launch_bounds__(kDrvThreads) void driven_adj_kernel(DrivenAdjArgs a
         for (int k = 0; k < K; ++k) {
           const float4 c = p[(int64_t)k * H];
 #pragma unroll
-          for (int s = 0; s < S; ++s) {
-            const float x = xs[s][i], v = vs[s][i];
-            const float cn = rcp(1.0f + ex2(gxs[s][i] + c.x));
-            const float m = ffma(v, cn, 1.0f);
-            const float z = ffma(c.z, m, c.y * x);
-            const float th = ffma(rcp(1.0f + ex2(z)), -2.0f, 1.0f);
-            // d m / d x = -wc gs cn (1 - u) ((1 - cn) + u)
-            const float dm = -(v * gs) * (cn * ((1.0f - cn) + us[s][i]));
-            d[s] = ffma(c.w * ffma(-th, th, 1.0f), ffma(c.z, dm, c.y), d[s]);
-          }
+          for (int s = 0; s < S; ++s) d[s] = drv_elem_vjp(c, xs[s][i], gxs[s][i], vs[s][i], us[s][i], gs, d[s]);
         }
       }
 #pragma unroll
@@ -508,150 +456,115 @@ int choose_spw(int64_t B) {
   return B <= 512 ? 1 : (B <= 1024 ? 2 : 4);
 }
 
+// the kernel tables (fetode_driven.h): rows by samples per workgroup, tables by [TAPE or XG][GRID]
 template <int S, bool TAPE, bool GRID>
-void launch_fixed_s(int K, int64_t grid, hipStream_t st, const DrivenArgs& a) {
-  const dim3 g((unsigned)grid), t(kDrvThreads);
-  if (K == 10) hipLaunchKernelGGL((driven_fixed_kernel<S, 10, TAPE, GRID>), g, t, 0, st, a);
-  else if (K == 12) hipLaunchKernelGGL((driven_fixed_kernel<S, 12, TAPE, GRID>), g, t, 0, st, a);
-  else hipLaunchKernelGGL((driven_fixed_kernel<S, 0, TAPE, GRID>), g, t, 0, st, a);
+constexpr DrvKRow<DrivenArgs> fixed_row() {
+  return {driven_fixed_kernel<S, 10, TAPE, GRID>, driven_fixed_kernel<S, 12, TAPE, GRID>,
+          driven_fixed_kernel<S, 0, TAPE, GRID>};
 }
-template <bool TAPE, bool GRID = false>
-void launch_fixed(int spw, int K, int64_t grid, hipStream_t st, const DrivenArgs& a) {
-  if (spw == 1) launch_fixed_s<1, TAPE, GRID>(K, grid, st, a);
-  else if (spw == 2) launch_fixed_s<2, TAPE, GRID>(K, grid, st, a);
-  else launch_fixed_s<4, TAPE, GRID>(K, grid, st, a);
+template <bool TAPE, bool GRID>
+constexpr DrvSRows<DrivenArgs> fixed_rows() {
+  return {fixed_row<1, TAPE, GRID>(), fixed_row<2, TAPE, GRID>(), fixed_row<4, TAPE, GRID>()};
 }
-
 template <int S, bool XG, bool GRID>
-void launch_adj_s(int K, int64_t grid, hipStream_t st, const DrivenAdjArgs& a) {
-  const dim3 g((unsigned)grid), t(kDrvThreads);
-  if (K == 10) hipLaunchKernelGGL((driven_adj_kernel<S, 10, XG, GRID>), g, t, 0, st, a);
-  else if (K == 12) hipLaunchKernelGGL((driven_adj_kernel<S, 12, XG, GRID>), g, t, 0, st, a);
-  else hipLaunchKernelGGL((driven_adj_kernel<S, 0, XG, GRID>), g, t, 0, st, a);
+constexpr DrvKRow<DrivenAdjArgs> adj_row() {
+  return {driven_adj_kernel<S, 10, XG, GRID>, driven_adj_kernel<S, 12, XG, GRID>, driven_adj_kernel<S, 0, XG, GRID>};
 }
-template <bool XG, bool GRID = false>
-void launch_adj(int spw, int K, int64_t grid, hipStream_t st, const DrivenAdjArgs& a) {
-  if (spw == 1) launch_adj_s<1, XG, GRID>(K, grid, st, a);
-  else if (spw == 2) launch_adj_s<2, XG, GRID>(K, grid, st, a);
-  else launch_adj_s<4, XG, GRID>(K, grid, st, a);
+template <bool XG, bool GRID>
+constexpr DrvSRows<DrivenAdjArgs> adj_rows() {
+  return {adj_row<1, XG, GRID>(), adj_row<2, XG, GRID>(), adj_row<4, XG, GRID>()};
+}
+const DrvSRows<DrivenArgs> kFixed[2][2] = {{fixed_rows<false, false>(), fixed_rows<false, true>()},
+                                           {fixed_rows<true, false>(), fixed_rows<true, true>()}};
+const DrvSRows<DrivenAdjArgs> kAdj[2][2] = {{adj_rows<false, false>(), adj_rows<false, true>()},
+                                            {adj_rows<true, false>(), adj_rows<true, true>()}};
+
+// What a solve or sweep entry decides first, and the launch shape.  grd: the fetode_driven_grid entries
+// (the four fixed-grid methods on a (n_steps, 4) coefficient array) instead of the fetode_driven_fixed
+// ones (rk4, 3/8 rule, on dt); each family keeps its own order of status decisions (pinned by
+// tests/test_driven_host.py and tests/test_driven_methods_host.py).  Here: shape, method, then the grid
+// entries' 2^31 limits.
+int driven_admit(bool grd, const fetode_ferro_t* fl, int32_t method, int64_t B, int32_t n_steps, int* spw,
+                 int64_t* grid) {
+  const char* who = grd ? "driven grid" : "driven";
+  if (!drv_shape_ok(fl)) return set_err(FETODE_EUNSUPPORTED, "%s: shape outside the admitted family", who);
+  if (!grd && method != FETODE_RK4) return set_err(FETODE_EUNSUPPORTED, "driven: only rk4 (3/8 rule) is fused");
+  if (grd && drv_nm_log2(method) < 0)
+    return set_err(FETODE_EUNSUPPORTED, "driven grid: method %d is not euler, midpoint, rk4 or rk4_classic", method);
+  // the launch shape; a B <= 0 gets a harmless one here and is refused or accepted as empty by the caller
+  *spw = choose_spw(B > 0 ? B : 1);
+  *grid = B > 0 ? (B + *spw - 1) / *spw : 0;
+  if (grd && (*grid > 0x7fffffff || (n_steps > 0 && ((int64_t)n_steps << drv_nm_log2(method)) > 0x7fffffff)))
+    return set_err(FETODE_EUNSUPPORTED, "driven grid: batch or evaluation count beyond 2^31 - 1");
+  return FETODE_OK;
 }
 
-int driven_fixed(const fetode_ferro_t* fl, const void* plan, int32_t method, const float* h0, int64_t B, const float* u,
-                 int64_t n_eval, int64_t eval0, const float* dt, int32_t n_steps, const float* prev0, float* sol,
-                 float* prev_out, float* tape_hx, float* tape_phi, bool tape, void* stream) {
-  if (!drv_shape_ok(fl)) return set_err(FETODE_EUNSUPPORTED, "driven: shape outside the admitted family");
-  if (method != FETODE_RK4) return set_err(FETODE_EUNSUPPORTED, "driven: only rk4 (3/8 rule) is fused");
-  if (B < 0 || n_steps < 0 || eval0 < 0 || eval0 + 4 * (int64_t)n_steps > n_eval)
-    return set_err(FETODE_EINVAL, "driven: evaluations %lld + 4 * %d exceed the table's %lld rows", (long long)eval0,
-                   n_steps, (long long)n_eval);
-  if (B == 0 || n_steps == 0) return FETODE_OK;
+// fixed: sizes, then OK when empty, then null pointers; grid: OK when empty, then the table's rows, then
+// null pointers.  Every status is decided before a launch.
+int driven_solve(bool grd, const fetode_ferro_t* fl, const void* plan, int32_t method, const float* h0, int64_t B,
+                 const float* u, int64_t n_eval, int64_t eval0, const float* dt, int32_t n_steps, const float* prev0,
+                 float* sol, float* prev_out, float* tape_hx, float* tape_phi, bool tape, void* stream) {
+  const char* who = grd ? "driven grid" : "driven";
+  int spw = 1;
+  int64_t grid = 0;
+  const int rc = driven_admit(grd, fl, method, B, n_steps, &spw, &grid);
+  if (rc != FETODE_OK) return rc;
+  const int sh = grd ? drv_nm_log2(method) : 2;
+  const bool empty = B <= 0 || n_steps <= 0;
+  const bool rows = eval0 < 0 || eval0 + (int64_t)n_steps * (1 << sh) > n_eval;
+  // fixed: bad sizes are refused before an empty solve is accepted
+  const bool sizes = !grd && (B < 0 || n_steps < 0 || rows);
+  // grid: an empty solve is accepted first (driven_admit has held B and the evaluation count below 2^31)
+  const bool grid_rows = grd && !empty && rows;
+  if (sizes || grid_rows)
+    return set_err(FETODE_EINVAL, "%s: evaluations %lld + %d * %d exceed the table's %lld rows", who, (long long)eval0,
+                   1 << sh, n_steps, (long long)n_eval);
+  if (empty) return FETODE_OK;
   if (!plan || !h0 || !u || !dt || !sol || (tape && (!tape_hx || !tape_phi)))
-    return set_err(FETODE_EINVAL, "driven: null pointer");
-  const int spw = choose_spw(B);
-  const int64_t grid = (B + spw - 1) / spw;
+    return set_err(FETODE_EINVAL, "%s: null pointer", who);
+  // fixed only: the grid entries were refused for this in driven_admit, before their empty and row checks
   if (grid > 0x7fffffff) return set_err(FETODE_EUNSUPPORTED, "driven: batch too large");
   DrivenArgs a{};
   a.plan = (const float*)plan;
   a.h0 = h0; a.u = u; a.dt = dt; a.prev0 = prev0; a.sol = sol; a.prev_out = prev_out;
   a.tape_hx = tape_hx; a.tape_phi = tape_phi;
-  a.B = B; a.eval0 = eval0;
-  a.H = fl->out_dim; a.D = fl->in_dim - fl->out_dim; a.K = fl->num_basis; a.n_steps = n_steps;
-  a.gs = (float)fl->gate_slope; a.gsl2e = (float)fl->gate_slope * FETODE_LOG2E;
-  a.wc = (float)(-2.0 * (1.0 - fl->alpha));
-  if (tape) launch_fixed<true>(spw, a.K, grid, (hipStream_t)stream, a);
-  else launch_fixed<false>(spw, a.K, grid, (hipStream_t)stream, a);
+  a.B = B; a.eval0 = eval0; a.n_steps = n_steps;
+  drv_fill_field(a, fl);
+  if (grd) {
+    a.method = method;
+    a.nm_log2 = sh;
+  }
+  drv_launch(kFixed[tape][grd].at(spw), a.K, dim3((unsigned)grid), kDrvThreads, (hipStream_t)stream, a);
   LAUNCH_CHECK();
   return FETODE_OK;
 }
 
-int driven_backward(const fetode_ferro_t* basis, const void* plan, int32_t method, int64_t B, const float* dt,
+// fixed: sizes, then OK for an empty batch (no steps: grad_h0 = grad_sol[0] is still written), then null
+// pointers; grid: OK when empty, then null pointers.
+int driven_backward(bool grd, const fetode_ferro_t* basis, const void* plan, int32_t method, int64_t B, const float* dt,
                     int32_t n_steps, const float* prev0, const float* tape_hx, const float* tape_phi,
                     const float* grad_sol, float* adj, float* grad_h0, float* adj_u, bool xg, void* stream) {
-  if (!drv_shape_ok(basis)) return set_err(FETODE_EUNSUPPORTED, "driven: shape outside the admitted family");
-  if (method != FETODE_RK4) return set_err(FETODE_EUNSUPPORTED, "driven: only rk4 (3/8 rule) is fused");
-  if (B < 0 || n_steps < 0) return set_err(FETODE_EINVAL, "driven backward: bad sizes");
-  if (B == 0) return FETODE_OK;
+  int spw = 1;
+  int64_t grid = 0;
+  const int rc = driven_admit(grd, basis, method, B, n_steps, &spw, &grid);
+  if (rc != FETODE_OK) return rc;
+  if (!grd && (B < 0 || n_steps < 0)) return set_err(FETODE_EINVAL, "driven backward: bad sizes");
+  if (grd ? (B <= 0 || n_steps <= 0) : B == 0) return FETODE_OK;
   if (!plan || !dt || !tape_hx || !tape_phi || !grad_sol || !adj || !grad_h0 || (xg && !adj_u))
-    return set_err(FETODE_EINVAL, "driven backward: null pointer");
-  const int spw = choose_spw(B);
-  const int64_t grid = (B + spw - 1) / spw;
+    return set_err(FETODE_EINVAL, "%s backward: null pointer", grd ? "driven grid" : "driven");
+  // fixed only, as in driven_solve
   if (grid > 0x7fffffff) return set_err(FETODE_EUNSUPPORTED, "driven: batch too large");
   DrivenAdjArgs a{};
   a.plan = (const float*)plan;
   a.dt = dt; a.prev0 = prev0; a.tape_hx = tape_hx; a.tape_phi = tape_phi; a.grad_sol = grad_sol;
   a.adj = adj; a.grad_h0 = grad_h0; a.adj_u = adj_u;
-  a.B = B;
-  a.H = basis->out_dim; a.D = basis->in_dim - basis->out_dim; a.K = basis->num_basis; a.n_steps = n_steps;
-  a.gs = (float)basis->gate_slope; a.gsl2e = (float)basis->gate_slope * FETODE_LOG2E;
-  a.wc = (float)(-2.0 * (1.0 - basis->alpha));
-  if (xg) launch_adj<true>(spw, a.K, grid, (hipStream_t)stream, a);
-  else launch_adj<false>(spw, a.K, grid, (hipStream_t)stream, a);
-  LAUNCH_CHECK();
-  return FETODE_OK;
-}
-
-// The four fixed-grid methods on a (n_steps, 4) coefficient array; every status is decided before a launch.
-int driven_grid_checks(const fetode_ferro_t* fl, int32_t method, int64_t B, int32_t n_steps, int* spw, int64_t* grid) {
-  if (!drv_shape_ok(fl)) return set_err(FETODE_EUNSUPPORTED, "driven grid: shape outside the admitted family");
-  if (drv_nm_log2(method) < 0)
-    return set_err(FETODE_EUNSUPPORTED, "driven grid: method %d is not euler, midpoint, rk4 or rk4_classic", method);
-  *spw = choose_spw(B > 0 ? B : 1);
-  *grid = B > 0 ? (B + *spw - 1) / *spw : 0;
-  if (*grid > 0x7fffffff || (n_steps > 0 && ((int64_t)n_steps << drv_nm_log2(method)) > 0x7fffffff))
-    return set_err(FETODE_EUNSUPPORTED, "driven grid: batch or evaluation count beyond 2^31 - 1");
-  return FETODE_OK;
-}
-
-int driven_grid(const fetode_ferro_t* fl, const void* plan, int32_t method, const float* h0, int64_t B, const float* u,
-                int64_t n_eval, int64_t eval0, const float* coef, int32_t n_steps, const float* prev0, float* sol,
-                float* prev_out, float* tape_hx, float* tape_phi, bool tape, void* stream) {
-  int spw = 1;
-  int64_t grid = 0;
-  const int rc = driven_grid_checks(fl, method, B, n_steps, &spw, &grid);
-  if (rc != FETODE_OK) return rc;
-  if (B <= 0 || n_steps <= 0) return FETODE_OK;
-  const int sh = drv_nm_log2(method);
-  if (eval0 < 0 || eval0 + ((int64_t)n_steps << sh) > n_eval)
-    return set_err(FETODE_EINVAL, "driven grid: evaluations %lld + %d * %d exceed the table's %lld rows",
-                   (long long)eval0, 1 << sh, n_steps, (long long)n_eval);
-  if (!plan || !h0 || !u || !coef || !sol || (tape && (!tape_hx || !tape_phi)))
-    return set_err(FETODE_EINVAL, "driven grid: null pointer");
-  DrivenArgs a{};
-  a.plan = (const float*)plan;
-  a.h0 = h0; a.u = u; a.dt = coef; a.prev0 = prev0; a.sol = sol; a.prev_out = prev_out;
-  a.tape_hx = tape_hx; a.tape_phi = tape_phi;
-  a.B = B; a.eval0 = eval0;
-  a.H = fl->out_dim; a.D = fl->in_dim - fl->out_dim; a.K = fl->num_basis; a.n_steps = n_steps;
-  a.gs = (float)fl->gate_slope; a.gsl2e = (float)fl->gate_slope * FETODE_LOG2E;
-  a.wc = (float)(-2.0 * (1.0 - fl->alpha));
-  a.method = method; a.nm_log2 = sh;
-  if (tape) launch_fixed<true, true>(spw, a.K, grid, (hipStream_t)stream, a);
-  else launch_fixed<false, true>(spw, a.K, grid, (hipStream_t)stream, a);
-  LAUNCH_CHECK();
-  return FETODE_OK;
-}
-
-int driven_grid_backward(const fetode_ferro_t* basis, const void* plan, int32_t method, int64_t B, const float* coef,
-                         int32_t n_steps, const float* prev0, const float* tape_hx, const float* tape_phi,
-                         const float* grad_sol, float* adj, float* grad_h0, float* adj_u, bool xg, void* stream) {
-  int spw = 1;
-  int64_t grid = 0;
-  const int rc = driven_grid_checks(basis, method, B, n_steps, &spw, &grid);
-  if (rc != FETODE_OK) return rc;
-  if (B <= 0 || n_steps <= 0) return FETODE_OK;
-  if (!plan || !coef || !tape_hx || !tape_phi || !grad_sol || !adj || !grad_h0 || (xg && !adj_u))
-    return set_err(FETODE_EINVAL, "driven grid backward: null pointer");
-  DrivenAdjArgs a{};
-  a.plan = (const float*)plan;
-  a.dt = coef; a.prev0 = prev0; a.tape_hx = tape_hx; a.tape_phi = tape_phi; a.grad_sol = grad_sol;
-  a.adj = adj; a.grad_h0 = grad_h0; a.adj_u = adj_u;
-  a.B = B;
-  a.H = basis->out_dim; a.D = basis->in_dim - basis->out_dim; a.K = basis->num_basis; a.n_steps = n_steps;
-  a.gs = (float)basis->gate_slope; a.gsl2e = (float)basis->gate_slope * FETODE_LOG2E;
-  a.wc = (float)(-2.0 * (1.0 - basis->alpha));
-  a.method = method; a.nm_log2 = drv_nm_log2(method);
-  if (xg) launch_adj<true, true>(spw, a.K, grid, (hipStream_t)stream, a);
-  else launch_adj<false, true>(spw, a.K, grid, (hipStream_t)stream, a);
+  a.B = B; a.n_steps = n_steps;
+  drv_fill_field(a, basis);
+  if (grd) {
+    a.method = method;
+    a.nm_log2 = drv_nm_log2(method);
+  }
+  drv_launch(kAdj[xg][grd].at(spw), a.K, dim3((unsigned)grid), kDrvThreads, (hipStream_t)stream, a);
   LAUNCH_CHECK();
   return FETODE_OK;
 }
@@ -704,7 +617,7 @@ int fetode_driven_table(const float* tq, int64_t n_eval, const float* t_grid, in
 int fetode_driven_fixed(const fetode_ferro_t* basis, const void* plan, int32_t method, const float* h0, int64_t B,
                         const float* u, int64_t n_eval, int64_t eval0, const float* dt, int32_t n_steps,
                         const float* prev0, float* sol, float* prev_out, void* stream) {
-  return driven_fixed(basis, plan, method, h0, B, u, n_eval, eval0, dt, n_steps, prev0, sol, prev_out, nullptr,
+  return driven_solve(false, basis, plan, method, h0, B, u, n_eval, eval0, dt, n_steps, prev0, sol, prev_out, nullptr,
                       nullptr, false, stream);
 }
 
@@ -712,7 +625,7 @@ int fetode_driven_fixed_tape(const fetode_ferro_t* basis, const void* plan, int3
                              const float* u, int64_t n_eval, int64_t eval0, const float* dt, int32_t n_steps,
                              const float* prev0, float* sol, float* prev_out, float* tape_hx, float* tape_phi,
                              void* stream) {
-  return driven_fixed(basis, plan, method, h0, B, u, n_eval, eval0, dt, n_steps, prev0, sol, prev_out, tape_hx,
+  return driven_solve(false, basis, plan, method, h0, B, u, n_eval, eval0, dt, n_steps, prev0, sol, prev_out, tape_hx,
                       tape_phi, true, stream);
 }
 
@@ -720,7 +633,7 @@ int fetode_driven_fixed_backward(const fetode_ferro_t* basis, const void* plan, 
                                  const float* dt, int32_t n_steps, const float* prev0, const float* tape_hx,
                                  const float* tape_phi, const float* grad_sol, float* adj, float* grad_h0,
                                  void* stream) {
-  return driven_backward(basis, plan, method, B, dt, n_steps, prev0, tape_hx, tape_phi, grad_sol, adj, grad_h0, nullptr,
+  return driven_backward(false, basis, plan, method, B, dt, n_steps, prev0, tape_hx, tape_phi, grad_sol, adj, grad_h0, nullptr,
                          false, stream);
 }
 
@@ -728,14 +641,14 @@ int fetode_driven_fixed_backward_x(const fetode_ferro_t* basis, const void* plan
                                    const float* dt, int32_t n_steps, const float* prev0, const float* tape_hx,
                                    const float* tape_phi, const float* grad_sol, float* adj, float* grad_h0,
                                    float* adj_u, void* stream) {
-  return driven_backward(basis, plan, method, B, dt, n_steps, prev0, tape_hx, tape_phi, grad_sol, adj, grad_h0, adj_u,
+  return driven_backward(false, basis, plan, method, B, dt, n_steps, prev0, tape_hx, tape_phi, grad_sol, adj, grad_h0, adj_u,
                          true, stream);
 }
 
 int fetode_driven_grid(const fetode_ferro_t* basis, const void* plan, int32_t method, const float* h0, int64_t B,
                        const float* u, int64_t n_eval, int64_t eval0, const float* coef, int32_t n_steps,
                        const float* prev0, float* sol, float* prev_out, void* stream) {
-  return driven_grid(basis, plan, method, h0, B, u, n_eval, eval0, coef, n_steps, prev0, sol, prev_out, nullptr,
+  return driven_solve(true, basis, plan, method, h0, B, u, n_eval, eval0, coef, n_steps, prev0, sol, prev_out, nullptr,
                      nullptr, false, stream);
 }
 
@@ -743,7 +656,7 @@ int fetode_driven_grid_tape(const fetode_ferro_t* basis, const void* plan, int32
                             const float* u, int64_t n_eval, int64_t eval0, const float* coef, int32_t n_steps,
                             const float* prev0, float* sol, float* prev_out, float* tape_hx, float* tape_phi,
                             void* stream) {
-  return driven_grid(basis, plan, method, h0, B, u, n_eval, eval0, coef, n_steps, prev0, sol, prev_out, tape_hx,
+  return driven_solve(true, basis, plan, method, h0, B, u, n_eval, eval0, coef, n_steps, prev0, sol, prev_out, tape_hx,
                      tape_phi, true, stream);
 }
 
@@ -751,7 +664,7 @@ int fetode_driven_grid_backward(const fetode_ferro_t* basis, const void* plan, i
                                 const float* coef, int32_t n_steps, const float* prev0, const float* tape_hx,
                                 const float* tape_phi, const float* grad_sol, float* adj, float* grad_h0,
                                 void* stream) {
-  return driven_grid_backward(basis, plan, method, B, coef, n_steps, prev0, tape_hx, tape_phi, grad_sol, adj, grad_h0,
+  return driven_backward(true, basis, plan, method, B, coef, n_steps, prev0, tape_hx, tape_phi, grad_sol, adj, grad_h0,
                               nullptr, false, stream);
 }
 
@@ -759,7 +672,7 @@ int fetode_driven_grid_backward_x(const fetode_ferro_t* basis, const void* plan,
                                   const float* coef, int32_t n_steps, const float* prev0, const float* tape_hx,
                                   const float* tape_phi, const float* grad_sol, float* adj, float* grad_h0,
                                   float* adj_u, void* stream) {
-  return driven_grid_backward(basis, plan, method, B, coef, n_steps, prev0, tape_hx, tape_phi, grad_sol, adj, grad_h0,
+  return driven_backward(true, basis, plan, method, B, coef, n_steps, prev0, tape_hx, tape_phi, grad_sol, adj, grad_h0,
                               adj_u, true, stream);
 }
 

@@ -7,7 +7,8 @@
 // end and runs that sample's control loop, so no workgroup waits on another one (no grid barrier, no
 // exchange, no co-residency limit).  The field is not autonomous: the stage times decide x(t), which
 // the kernel interpolates from the sample's own (T, D) series at every evaluation time.
-//   evaluation   driven_fixed_kernel's arithmetic at one sample per workgroup: the plan of
+//   evaluation   fetode_driven_dev.h's gate, element loop and meeting (the functions driven_fixed_kernel
+//                calls) at one sample per workgroup: the plan of
 //                fetode_driven_plan_build, lane -> output o, wave w -> inputs i = w (mod 4), the gate
 //                against the previous evaluation's input (prev <- hx in call order, rejected and probe
 //                evaluations included), the fixed-order meeting of the four partial sums in LDS
@@ -19,9 +20,8 @@
 //                is included once per kernel signature, the tape's statements as preprocessor blocks
 #include <string.h>
 
-#include "fetode_common.h"
 #include "fetode_dopri_ctl.h"
-#include "fetode_driven.h"
+#include "fetode_driven_dev.h"
 
 using namespace fetode;
 
@@ -57,13 +57,6 @@ struct DrivenDopriTape {
   int32_t max_ev;
 };
 
-// the butterfly gives every lane the same bits: each level adds the same two values on both sides
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
-
 // phases of a sample's solve; every thread follows them, wave 0 announces through s_nq how many
 // evaluations the next one has (0: the solve is over)
 enum { kPhaseF0 = 0, kPhaseProbe = 1, kPhaseAttempt = 2 };
@@ -83,20 +76,12 @@ __global__ __launch_bounds__(kDrvThreads) void driven_dopri5_tape_kernel(DrivenD
 #undef FETODE_DRIVEN_TAPE
 }
 
-template <bool EVLOG>
-void launch_dopri5(int K, int64_t B, hipStream_t st, const DrivenDopriArgs& a) {
-  const dim3 g((unsigned)B), t(kDrvThreads);
-  if (K == 10) hipLaunchKernelGGL((driven_dopri5_kernel<10, EVLOG>), g, t, 0, st, a);
-  else if (K == 12) hipLaunchKernelGGL((driven_dopri5_kernel<12, EVLOG>), g, t, 0, st, a);
-  else hipLaunchKernelGGL((driven_dopri5_kernel<0, EVLOG>), g, t, 0, st, a);
-}
-
-void launch_dopri5_tape(int K, int64_t B, hipStream_t st, const DrivenDopriArgs& a, const DrivenDopriTape& tp) {
-  const dim3 g((unsigned)B), t(kDrvThreads);
-  if (K == 10) hipLaunchKernelGGL((driven_dopri5_tape_kernel<10>), g, t, 0, st, a, tp);
-  else if (K == 12) hipLaunchKernelGGL((driven_dopri5_tape_kernel<12>), g, t, 0, st, a, tp);
-  else hipLaunchKernelGGL((driven_dopri5_tape_kernel<0>), g, t, 0, st, a, tp);
-}
+// the kernel tables (fetode_driven.h): [EVLOG] and the taped row
+const DrvKRow<DrivenDopriArgs> kDopri5[2] = {
+    {driven_dopri5_kernel<10, false>, driven_dopri5_kernel<12, false>, driven_dopri5_kernel<0, false>},
+    {driven_dopri5_kernel<10, true>, driven_dopri5_kernel<12, true>, driven_dopri5_kernel<0, true>}};
+const DrvKRow<DrivenDopriArgs, DrivenDopriTape> kDopri5Tape = {
+    driven_dopri5_tape_kernel<10>, driven_dopri5_tape_kernel<12>, driven_dopri5_tape_kernel<0>};
 
 // steps counted per output interval beyond which only the geometric shrink of a rejected step bounds
 // the loop (DESIGN §4.18 "Termination")
@@ -128,11 +113,10 @@ int driven_dopri5(const fetode_ferro_t* basis, const void* plan, const float* h0
   a.plan = (const float*)plan;
   a.h0 = h0; a.x = x; a.tg = t_grid; a.prev0 = prev0; a.sol = sol; a.prev_out = prev_out;
   a.stats = stats; a.att = attempts; a.evlog = evlog;
-  a.H = basis->out_dim; a.D = basis->in_dim - basis->out_dim; a.K = basis->num_basis; a.T = T;
+  drv_fill_field(a, basis);
+  a.T = T;
   a.max_att = attempts ? max_attempts : 0;
   a.max_ev = evlog ? max_ev : 0;
-  a.gs = (float)basis->gate_slope; a.gsl2e = (float)basis->gate_slope * FETODE_LOG2E;
-  a.wc = (float)(-2.0 * (1.0 - basis->alpha));
   a.rtol = (float)rtol; a.atol = (float)atol;
   memcpy(a.beta, tableau, sizeof(a.beta));
   memcpy(a.cerr, tableau + 36, sizeof(a.cerr));
@@ -140,9 +124,9 @@ int driven_dopri5(const fetode_ferro_t* basis, const void* plan, const float* h0
   // torchdiffeq's alpha (dopri5.py _A) rounded to fp32 like the rest of the tableau
   const double alpha[6] = {1.0 / 5, 3.0 / 10, 4.0 / 5, 8.0 / 9, 1.0, 1.0};
   for (int i = 0; i < 6; ++i) a.alpha[i] = (float)alpha[i];
-  if (tape) launch_dopri5_tape(a.K, B, (hipStream_t)stream, a, *tape);
-  else if (evlog) launch_dopri5<true>(a.K, B, (hipStream_t)stream, a);
-  else launch_dopri5<false>(a.K, B, (hipStream_t)stream, a);
+  const dim3 grid((unsigned)B);
+  if (tape) drv_launch(kDopri5Tape, a.K, grid, kDrvThreads, (hipStream_t)stream, a, *tape);
+  else drv_launch(kDopri5[evlog != nullptr], a.K, grid, kDrvThreads, (hipStream_t)stream, a);
   LAUNCH_CHECK();
   return FETODE_OK;
 }

@@ -2,8 +2,8 @@
 // per kernel signature: the including kernel provides KT, EVLOG and the arguments `a`; the taped kernel
 // defines FETODE_DRIVEN_TAPE and provides the tape `tp`.  The tape's statements are preprocessor blocks,
 // so the untaped kernels compile from exactly the tokens they had before the tape existed.
-  __shared__ float xs[kDrvInMax], gxs[kDrvInMax], vs[kDrvInMax];
-  __shared__ float part[4][64];
+  __shared__ float xs[1][kDrvInMax], gxs[1][kDrvInMax], vs[1][kDrvInMax];  // one sample per workgroup
+  __shared__ float part[4][1][64];
   __shared__ float s_beta[6][6], s_cerr[7], s_cmid[7], s_alpha[6];
   __shared__ float s_tq[6], us[6][kDrvDMax];  // the phase's evaluation times and x(t) at each
   __shared__ int s_nq;
@@ -27,13 +27,13 @@
   // input i of the next evaluation: value, its gate against the previous evaluation's input
   // (prev <- hx, call order) and the per-input factors of the element loop
   auto publish = [&](int i, float xn, float xo) {
-    const float up = 1.0f / (1.0f + expf(-(gs * (xn - xo))));
-    xs[i] = xn;
-    gxs[i] = gsl2e * xn;
-    vs[i] = wc * (1.0f - up);
+    const DrvGate g = drv_gate(gs, gsl2e, wc, xn, xo);
+    xs[0][i] = g.x;
+    gxs[0][i] = g.gx;
+    vs[0][i] = g.v;
   };
-  // LinearInterp1D (compare_noise_ecg.py:861-872) as driven_table_kernel states it; the left
-  // searchsorted of an increasing grid by bisection (every index stays inside [0, T - 1])
+  // LinearInterp1D (compare_noise_ecg.py:861-872) as drv_locate states it, but the left searchsorted
+  // of an increasing grid by bisection (every index stays inside [0, T - 1])
 #ifdef FETODE_DRIVEN_TAPE
   float slope = 0.f;  // the slope of the interval the last interp used
 #endif
@@ -84,39 +84,23 @@
         }
       }
 #endif
-      if (s == 0) publish(H + d, v, first ? (a.prev0 ? a.prev0[b * In + H + d] : 0.f) : xs[H + d]);
+      if (s == 0) publish(H + d, v, first ? (a.prev0 ? a.prev0[b * In + H + d] : 0.f) : xs[0][H + d]);
     }
   };
   // one evaluation of the published input; wave 0 receives f (lanes >= H: 0)
   auto eval = [&]() -> float {
     __syncthreads();  // this evaluation's inputs are published
 #ifdef FETODE_DRIVEN_TAPE
-    if (tid < In && nfev < tp.max_ev) tp.hx[(b * tp.max_ev + nfev) * In + tid] = xs[tid];
+    if (tid < In && nfev < tp.max_ev) tp.hx[(b * tp.max_ev + nfev) * In + tid] = xs[0][tid];
 #endif
-    float acc = 0.f;
-    if (lane < H) {
-      for (int i = wv; i < In; i += 4) {
-        const float x = xs[i], gx = gxs[i], v = vs[i];
-        float ai = 0.f;
-        const float4* __restrict__ p = el + (int64_t)i * K * H + lane;
-#pragma unroll KT > 0 ? KT : 1
-        for (int k = 0; k < K; ++k) {
-          const float4 c = p[(int64_t)k * H];
-          const float cn = rcp(1.0f + ex2(gx + c.x));               // sigma(gs(-x - Ec))
-          const float m = ffma(v, cn, 1.0f);
-          const float z = ffma(c.z, m, c.y * x);                    // 2 log2e k (x + Ec m)
-          const float th = ffma(rcp(1.0f + ex2(z)), -2.0f, 1.0f);   // tanh(k (x + Ec m))
-          ai = ffma(c.w, th, ai);
-        }
-        acc += ai;
-      }
-    }
-    part[wv][lane] = acc;
+    float acc[1];
+    drv_eval_partial<1, KT>(el, H, In, K, lane, wv, xs, gxs, vs, acc);
+    part[wv][0][lane] = acc[0];
     __syncthreads();  // partial sums are in; nobody reads this evaluation's inputs any more
     ++nfev;
     float f = 0.f;
     if (w0) {
-      const float phi = ((part[0][lane] + part[1][lane]) + (part[2][lane] + part[3][lane])) + fcon;
+      const float phi = drv_eval_meet<1>(part, 0, lane, fcon);
 #ifdef FETODE_DRIVEN_TAPE
       // nfev counts this evaluation already
       if (own && nfev <= tp.max_ev) tp.phi[(b * tp.max_ev + (nfev - 1)) * H + lane] = phi;
@@ -167,7 +151,7 @@
       err = f0 * (s_cerr[0] * dt32);
       mid = f0 * (s_cmid[0] * dt32);
       yi = y + A[0];
-      if (own) publish(lane, yi, xs[lane]);
+      if (own) publish(lane, yi, xs[0][lane]);
     }
     if (lane == 0) s_nq = n;
   };
@@ -229,7 +213,7 @@
             tp.init_rec[b * 5 + 3] = h0p;
           }
 #endif
-          if (own) publish(lane, y + f0 * h0p, xs[lane]);
+          if (own) publish(lane, y + f0 * h0p, xs[0][lane]);
           if (lane == 0) {
             s_tq[0] = (float)(t0s + (double)h0p);
             s_nq = 1;
@@ -268,10 +252,10 @@
           mid = mid + kn * (s_cmid[j] * dt32);
           if (s < 5) {
             yi = y + A[0];
-            if (own) publish(lane, yi, xs[lane]);
+            if (own) publish(lane, yi, xs[0][lane]);
           }
         }
-        if (drv && s < 5) publish(H + dd, us[s + 1][dd], xs[H + dd]);
+        if (drv && s < 5) publish(H + dd, us[s + 1][dd], xs[0][H + dd]);
       }
       if (w0) {
         const float y1 = yi;
@@ -302,7 +286,7 @@
     }
   }
   // prev <- the last evaluation's input (the end publishes nothing)
-  if (a.prev_out && tid < In) a.prev_out[b * In + tid] = xs[tid];
+  if (a.prev_out && tid < In) a.prev_out[b * In + tid] = xs[0][tid];
   if (tid == 0) {
     a.stats[b * 3 + 0] = nfev;
     a.stats[b * 3 + 1] = n_att;

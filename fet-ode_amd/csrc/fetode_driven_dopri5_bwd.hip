@@ -13,8 +13,8 @@
 // and walks that sample's evaluations backwards from its own status words; no workgroup waits on
 // another one.  Wave 0 holds the element adjoints (one lane per element) and the fp64 control scalars
 // (equal on all its lanes, sums by the forward's butterfly); the four waves share the evaluation's VJP
-// in driven_adj_kernel's mapping (lane -> output, wave w -> inputs i = w (mod 4), one wave sum per
-// input; the gate's x differentiated, prev detached), over the H state inputs, and over the D driving
+// by drv_elem_vjp (fetode_driven_dev.h) in driven_adj_kernel's loop and mapping (lane -> output, wave
+// w -> inputs i = w (mod 4), one wave sum per input), over the H state inputs, and over the D driving
 // inputs too when the step-size gradient is on or adj_u is asked for (fetode_driven_dopri5_backward_x:
 // d loss / d x(t) of every evaluation, which fetode_driven_table_backward takes to the series' knots).
 // step_grad = 0 freezes the step sequence: every dt, t0 and stage time is a constant, so there is no
@@ -24,9 +24,8 @@
 // (fetode_driven_param_grad, fetode_driven_pgrad.hip, or the generic Ferro backward).
 #include <string.h>
 
-#include "fetode_common.h"
 #include "fetode_dopri_ctl.h"
-#include "fetode_driven.h"
+#include "fetode_driven_dev.h"
 
 using namespace fetode;
 
@@ -52,18 +51,6 @@ struct DrivenDopriAdjArgs {
   double ifactor, dfactor, min_step, max_step;
   float beta[6][6], cerr[7], cmid[7], alpha[6];
 };
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
-// the forward's butterfly: every lane ends with the same bits
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
 
 template <int KT>
 __global__ __launch_bounds__(kDrvThreads) void driven_dopri5_adj_kernel(DrivenDopriAdjArgs a) {
@@ -294,11 +281,11 @@ __global__ __launch_bounds__(kDrvThreads) void driven_dopri5_adj_kernel(DrivenDo
     if (tid < In) {
       const float xv = thx[(int64_t)ev * In + tid];
       const float pv = ev > 0 ? thx[(int64_t)(ev - 1) * In + tid] : (a.prev0 ? a.prev0[b * In + tid] : 0.f);
-      const float up = 1.0f / (1.0f + expf(-(gs * (xv - pv))));
-      xs[tid] = xv;
-      gxs[tid] = gsl2e * xv;
-      vs[tid] = wc * (1.0f - up);
-      us[tid] = up;
+      const DrvGate g = drv_gate(gs, gsl2e, wc, xv, pv);
+      xs[tid] = g.x;
+      gxs[tid] = g.gx;
+      vs[tid] = g.v;
+      us[tid] = g.u;
     }
     __syncthreads();
     const float gp = gph[lane];
@@ -308,16 +295,7 @@ __global__ __launch_bounds__(kDrvThreads) void driven_dopri5_adj_kernel(DrivenDo
         const float x = xs[i], v = vs[i], gx = gxs[i], u = us[i];
         const float4* __restrict__ p = el + (int64_t)i * K * H + lane;
 #pragma unroll KT > 0 ? KT : 1
-        for (int k = 0; k < K; ++k) {
-          const float4 c = p[(int64_t)k * H];
-          const float cn = rcp(1.0f + ex2(gx + c.x));
-          const float m = ffma(v, cn, 1.0f);
-          const float z = ffma(c.z, m, c.y * x);
-          const float th = ffma(rcp(1.0f + ex2(z)), -2.0f, 1.0f);
-          // d m / d x = -wc gs cn (1 - u) ((1 - cn) + u)
-          const float dm = -(v * gs) * (cn * ((1.0f - cn) + u));
-          d = ffma(c.w * ffma(-th, th, 1.0f), ffma(c.z, dm, c.y), d);
-        }
+        for (int k = 0; k < K; ++k) d = drv_elem_vjp(p[(int64_t)k * H], x, gx, v, u, gs, d);
       }
       const float r = wave_sum(d * gp);
       if (lane == 0) gout[i] = r * (0.5f / FETODE_LOG2E);  // c.y, c.z carry 2 log2e
@@ -375,12 +353,8 @@ __global__ __launch_bounds__(kDrvThreads) void driven_dopri5_adj_kernel(DrivenDo
   }
 }
 
-void launch_adj(int K, int64_t B, hipStream_t st, const DrivenDopriAdjArgs& a) {
-  const dim3 g((unsigned)B), t(kDrvThreads);
-  if (K == 10) hipLaunchKernelGGL((driven_dopri5_adj_kernel<10>), g, t, 0, st, a);
-  else if (K == 12) hipLaunchKernelGGL((driven_dopri5_adj_kernel<12>), g, t, 0, st, a);
-  else hipLaunchKernelGGL((driven_dopri5_adj_kernel<0>), g, t, 0, st, a);
-}
+const DrvKRow<DrivenDopriAdjArgs> kDopri5Adj = {driven_dopri5_adj_kernel<10>, driven_dopri5_adj_kernel<12>,
+                                                driven_dopri5_adj_kernel<0>};
 
 int driven_dopri5_backward(const fetode_ferro_t* basis, const void* plan, int64_t B, const float* t_grid, int32_t T,
                            double rtol, double atol, const double* opts, const float* tableau, const float* prev0,
@@ -404,10 +378,9 @@ int driven_dopri5_backward(const fetode_ferro_t* basis, const void* plan, int64_
   a.tg = t_grid; a.prev0 = prev0; a.stats = stats; a.att = attempts; a.init_rec = init_rec;
   a.tape_hx = tape_hx; a.tape_phi = tape_phi; a.tape_sl = tape_slope; a.gsol = grad_sol;
   a.adj = adj; a.grad_h0 = grad_h0; a.adj_u = adj_u;
-  a.H = basis->out_dim; a.D = basis->in_dim - basis->out_dim; a.K = basis->num_basis; a.T = T;
+  drv_fill_field(a, basis);
+  a.T = T;
   a.max_att = max_attempts; a.max_ev = max_ev; a.base = dopri_base(opts); a.step_grad = step_grad ? 1 : 0;
-  a.gs = (float)basis->gate_slope; a.gsl2e = (float)basis->gate_slope * FETODE_LOG2E;
-  a.wc = (float)(-2.0 * (1.0 - basis->alpha));
   a.rtol = (float)rtol; a.atol = (float)atol;
   a.ifactor = step.ifactor; a.dfactor = step.dfactor; a.min_step = step.min_step; a.max_step = step.max_step;
   memcpy(a.beta, tableau, sizeof(a.beta));
@@ -415,7 +388,7 @@ int driven_dopri5_backward(const fetode_ferro_t* basis, const void* plan, int64_
   memcpy(a.cmid, tableau + 43, sizeof(a.cmid));
   const double alpha[6] = {1.0 / 5, 3.0 / 10, 4.0 / 5, 8.0 / 9, 1.0, 1.0};  // as the forward rounds them
   for (int i = 0; i < 6; ++i) a.alpha[i] = (float)alpha[i];
-  launch_adj(a.K, B, (hipStream_t)stream, a);
+  drv_launch(kDopri5Adj, a.K, dim3((unsigned)B), kDrvThreads, (hipStream_t)stream, a);
   LAUNCH_CHECK();
   return FETODE_OK;
 }

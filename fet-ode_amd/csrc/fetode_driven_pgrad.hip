@@ -19,9 +19,9 @@
 //   A  = sum g th                     d Ps   = coef A,         d coef = Ps A + bias G
 //   G  = sum g   (per output)         d bias = coef G
 // which is ferro_point_vjp's algebra with bs = 1.  The element terms use the forward's exp2 / rcp
-// forms; the gate's expf and the outer tanhf are the forward's precise ones.
-#include "fetode_common.h"
-#include "fetode_driven.h"
+// forms on the raw Ec and k (their own expression, not fetode_driven_dev.h's plan element); the gate is
+// the forward's drv_gate and the outer tanhf its precise one.
+#include "fetode_driven_dev.h"
 
 using namespace fetode;
 
@@ -101,8 +101,8 @@ __global__ __launch_bounds__(kPgThreads) void driven_pgrad_kernel(DrivenPgArgs a
         sbias += ad;
       }
       if (a.elems) {
-        const float u = 1.0f / (1.0f + expf(-(gs * (xv - pv))));
-        const float w = wc * (1.0f - u), wg = -(w * gs), gx = gs2 * xv;
+        const float w = drv_gate(gs, gs2, wc, xv, pv).v;   // the forward's gate (fetode_driven_dev.h)
+        const float wg = -(w * gs), gx = gs2 * xv;
 #pragma unroll
         for (int j = 0; j < KC; ++j) {
           const float sg = rcp(1.0f + ex2(gx + GE[j]));              // sigma(gs(-x - Ec))
@@ -205,6 +205,10 @@ __global__ __launch_bounds__(256) void driven_pgrad_reduce_kernel(DrivenPgArgs a
   }
 }
 
+// K = 10 and 12 whole in one workgroup, any other K in chunks of kPgChunk bases
+const DrvKRow<DrivenPgArgs> kPgrad = {driven_pgrad_kernel<10, true>, driven_pgrad_kernel<12, true>,
+                                      driven_pgrad_kernel<kPgChunk, false>};
+
 int g_splits = 0;  // forced row split (0: from the shape)
 
 // the largest split a launch over R rows uses, forced or not: the workspace is sized for it
@@ -277,10 +281,8 @@ int fetode_driven_param_grad(const fetode_ferro_t* basis, const float* gain, int
   a.part = (float*)workspace;
   a.side = a.part + (int64_t)a.S * 3 * In * K * H;
   // without element sums only the workgroups of input 0 (chunk 0) have anything to do
-  const dim3 grid(elems ? (unsigned)(In * pg_chunks(K)) : 1u, (unsigned)a.S), thr(kPgThreads);
-  if (K == 10) hipLaunchKernelGGL((driven_pgrad_kernel<10, true>), grid, thr, 0, st, a);
-  else if (K == 12) hipLaunchKernelGGL((driven_pgrad_kernel<12, true>), grid, thr, 0, st, a);
-  else hipLaunchKernelGGL((driven_pgrad_kernel<kPgChunk, false>), grid, thr, 0, st, a);
+  const dim3 grid(elems ? (unsigned)(In * pg_chunks(K)) : 1u, (unsigned)a.S);
+  drv_launch(kPgrad, K, grid, kPgThreads, st, a);
   LAUNCH_CHECK();
   const fetode_ferro_grad_t none{};
   const int64_t nt = (int64_t)In * K * H + H;

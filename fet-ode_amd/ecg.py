@@ -641,24 +641,45 @@ def _driven_rules(func, t, tc, reversed_) -> bool:
     return bool(_lib.load().fetode_driven_supported(_lib.ctypes.byref(func.basis.desc(keep))))
 
 
-def _driven_series(func, y0):
-    """The driving series (B, T, D) of an eligible solve, or None: every tensor fp32 on y0's GPU with
-    matching shapes; detached and contiguous unless it requires grad and set_driven_series_grad is on
-    (then attached; a 2-D series as its expand over the batch, so autograd sums the rows)."""
+def _driven_tensor_rules(func, y0):
+    """The tensor rules of every one-launch driven solve, stated once: the series (B, T, D) (a 2-D one as
+    its expand over y0's B rows, attached) and the seven parameters fp32 on y0's device, shapes matching
+    the basis and the interpolator's grid.  The series, or None."""
     x, tg = func._interp.x, func._interp.t
     B, H = y0.shape
     if x.dim() == 2:
         x = x.unsqueeze(0).expand(B, -1, -1)
     bas = func.basis
-    if (x.dim() != 3 or x.shape[0] != B or x.shape[1] != tg.numel() or x.shape[2] != bas.in_dim - bas.out_dim
-            or H != bas.out_dim or x.dtype != torch.float32 or x.device != y0.device):
+    if (x.dim() != 3 or tuple(x.shape) != (B, tg.numel(), bas.in_dim - bas.out_dim) or H != bas.out_dim
+            or x.dtype != torch.float32 or x.device != y0.device):
+        return None
+    if any(p.device != y0.device or p.dtype != torch.float32 for p in _driven_tensors(func)):
+        return None
+    return x
+
+
+def _driven_series(func, y0):
+    """The driving series (B, T, D) of an eligible solve, or None: _driven_tensor_rules; detached and
+    contiguous unless it requires grad and set_driven_series_grad is on (then attached, so autograd sums
+    the rows of a 2-D series)."""
+    x = _driven_tensor_rules(func, y0)
+    if x is None:
         return None
     xgrad = torch.is_grad_enabled() and x.requires_grad
     if xgrad and not _DRIVEN_XGRAD[0]:
         return None
-    if any(p.device != y0.device or p.dtype != torch.float32 for p in _driven_tensors(func)):
-        return None
     return x if xgrad else x.detach().contiguous()
+
+
+def _driven_recognise(eligible, func, y0, t, tc, step_size, reversed_, method_code):
+    """What driven_recognise and driven_grid_recognise share: y0 (B, H) fp32 on a GPU, the family's
+    `eligible` rules, then _driven_series.  (x (B, T, D), _driven_grid's tensors) or None."""
+    if y0.dim() != 2 or y0.dtype != torch.float32 or not y0.is_cuda:
+        return None
+    if not eligible(func, t, tc, step_size, reversed_, method_code):
+        return None
+    x = _driven_series(func, y0)
+    return None if x is None else (x, _driven_grid(tc, y0.device))
 
 
 def driven_recognise(func, y0, t, tc, step_size, reversed_, method_code):
@@ -666,12 +687,7 @@ def driven_recognise(func, y0, t, tc, step_size, reversed_, method_code):
     driven_eligible, and every tensor fp32 on y0's GPU with matching shapes; a driving series that
     requires grad is left to the per-stage path unless set_driven_series_grad is on, and is then
     returned attached (a 2-D series as its expand over the batch, so autograd sums the rows)."""
-    if y0.dim() != 2 or y0.dtype != torch.float32 or not y0.is_cuda:
-        return None
-    if not driven_eligible(func, t, tc, step_size, reversed_, method_code):
-        return None
-    x = _driven_series(func, y0)
-    return None if x is None else (x, _driven_grid(tc, y0.device))
+    return _driven_recognise(driven_eligible, func, y0, t, tc, step_size, reversed_, method_code)
 
 
 def _driven_prev0(f, h0, u):
@@ -682,26 +698,77 @@ def _driven_prev0(f, h0, u):
     return hx0 if f.basis._needs_reinit(hx0) else f.basis._prev.detach().clone()
 
 
-def _driven_launch(f, plan, d, h0, u, dtv, prev0, n_steps, tape):
+def _driven_family_launch(family, f, plan, d, method_code, h0, u, coef, prev0, n_steps, tape):
+    """One launch of fetode_driven_<family>[_tape], family "fixed" (rk4 on the step sizes `coef`) or "grid"
+    (method_code on the (n_steps, 4) coefficients): (sol (n_steps + 1, B, H) with row 0 = h0, tape_hx,
+    tape_phi or None); leaves the basis with the last evaluation's input."""
     lib = _lib.load()
     dev = h0.device
     B, H = h0.shape
     In = f.basis.in_dim
+    ne = n_steps * _GRID_STAGES[method_code]
     sol = torch.empty(n_steps + 1, B, H, device=dev, dtype=torch.float32)
     sol[0] = h0
     prev_out = torch.empty(B, In, device=dev, dtype=torch.float32)
-    args = [_lib.ctypes.byref(d), plan.data_ptr(), _lib.RK4, h0.data_ptr(), B, u.data_ptr(), u.shape[0], 0,
-            dtv.data_ptr(), n_steps, prev0.data_ptr(), sol[1:].data_ptr(), prev_out.data_ptr()]
+    args = [_lib.ctypes.byref(d), plan.data_ptr(), method_code, h0.data_ptr(), B, u.data_ptr(), u.shape[0], 0,
+            coef.data_ptr(), n_steps, prev0.data_ptr(), sol[1:].data_ptr(), prev_out.data_ptr()]
+    thx = tphi = None
     if tape:
-        thx = torch.empty(4 * n_steps, B, In, device=dev, dtype=torch.float32)
-        tphi = torch.empty(4 * n_steps, B, H, device=dev, dtype=torch.float32)
-        _lib.check(lib.fetode_driven_fixed_tape(*args, thx.data_ptr(), tphi.data_ptr(), _lib.stream_handle(dev)),
-                   "fetode_driven_fixed_tape")
-    else:
-        thx = tphi = None
-        _lib.check(lib.fetode_driven_fixed(*args, _lib.stream_handle(dev)), "fetode_driven_fixed")
+        thx = torch.empty(ne, B, In, device=dev, dtype=torch.float32)
+        tphi = torch.empty(ne, B, H, device=dev, dtype=torch.float32)
+        args += [thx.data_ptr(), tphi.data_ptr()]
+    name = "fetode_driven_%s%s" % (family, "_tape" if tape else "")
+    _lib.check(getattr(lib, name)(*args, _lib.stream_handle(dev)), name)
     f.basis._prev = prev_out   # prev_x <- the last evaluation's input (ferro_class.py:409)
     return sol, thx, tphi
+
+
+def _driven_launch(f, plan, d, h0, u, dtv, prev0, n_steps, tape):
+    return _driven_family_launch("fixed", f, plan, d, _lib.RK4, h0, u, dtv, prev0, n_steps, tape)
+
+
+def _driven_fixed_backward(family, ctx, method_code, coef, prev0, thx, tphi, grad, times, params, want):
+    """The backward of a fixed-layout tape ((n_ev, B, .) rows): the reverse sweep by
+    fetode_driven_<family>_backward, or _backward_x followed by driven_series_grad at times() = (t_grid,
+    stage times) where the series requires grad, then _driven_param_sums: (grad_h0, grad_x or None, the
+    seven parameter gradients)."""
+    lib = _lib.load()
+    dev = grad.device
+    g = _lib.f32c(grad)
+    ne, B, H = tphi.shape
+    adj = torch.empty_like(tphi)
+    gh0 = torch.empty(B, H, device=dev, dtype=torch.float32)
+    args = [_lib.ctypes.byref(ctx.d), ctx.plan.data_ptr(), method_code, B, coef.data_ptr(), ctx.n_steps,
+            prev0.data_ptr(), thx.data_ptr(), tphi.data_ptr(), g.data_ptr(), adj.data_ptr(), gh0.data_ptr()]
+    gx = None
+    name = "fetode_driven_%s_backward" % family
+    if ctx.needs_input_grad[1]:
+        D = thx.shape[2] - H
+        adj_u = torch.empty(ne, B, D, device=dev, dtype=torch.float32)
+        _lib.check(getattr(lib, name + "_x")(*args, adj_u.data_ptr(), _lib.stream_handle(dev)), name + "_x")
+        tg, tq = times()
+        gx = driven_series_grad(tq, 0, tg, adj_u, B, ne, 1, B, None, 0, D)
+    else:
+        _lib.check(getattr(lib, name)(*args, _lib.stream_handle(dev)), name)
+    grads = _driven_param_sums(ctx.f, ctx.d, params, want, B, ne, (1, B, None, 0), prev0, thx, tphi, adj,
+                               lambda hx: torch.cat([prev0.unsqueeze(0), hx[:-1]], dim=0))
+    return gh0, gx, grads
+
+
+def _driven_param_sums(f, d, params, want, B, ne, layout, prev0, thx, tphi, adj, prev_rows, rows=lambda t: t):
+    """The seven parameter gradients of a taped driven solve (None where want is false), the one choice of
+    every backward: nothing wanted; zeros without taped rows; driven_param_grads with
+    set_fused_driven_param_grads on, over ne rows per sample in the row layout (stride_b, stride_e, nfev,
+    nfev_stride); else the generic Ferro backward over rows(.) of the tapes, prev_rows(rows(thx)) their
+    hysteresis inputs."""
+    if not any(want):
+        return [None] * 7
+    if ne <= 0:
+        return [torch.zeros_like(p) if w else None for p, w in zip(params, want)]
+    if _DRIVEN_PARAM_GRADS[0]:
+        return driven_param_grads(d, [_lib.f32c(p) for p in params], want, B, ne, *layout, prev0, thx, tphi, adj)
+    thx = rows(thx)
+    return _driven_param_sums_generic(f, params[5], want, thx, rows(tphi), rows(adj), lambda: prev_rows(thx))
 
 
 def _driven_param_sums_generic(f, gain, want, thx, tphi, adj, prev_rows):
@@ -781,37 +848,9 @@ class _DrivenFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad):
-        lib = _lib.load()
         dtv, prev0, thx, tphi, *params = ctx.saved_tensors
-        f, n_steps = ctx.f, ctx.n_steps
-        dev = grad.device
-        g = _lib.f32c(grad)
-        ne, B, H = tphi.shape
-        In = thx.shape[2]
-        adj = torch.empty_like(tphi)
-        gh0 = torch.empty(B, H, device=dev, dtype=torch.float32)
-        args = [_lib.ctypes.byref(ctx.d), ctx.plan.data_ptr(), _lib.RK4, B, dtv.data_ptr(), n_steps, prev0.data_ptr(),
-                thx.data_ptr(), tphi.data_ptr(), g.data_ptr(), adj.data_ptr(), gh0.data_ptr()]
-        gx = None
-        if ctx.needs_input_grad[1]:
-            D = In - H
-            adj_u = torch.empty(ne, B, D, device=dev, dtype=torch.float32)
-            _lib.check(lib.fetode_driven_fixed_backward_x(*args, adj_u.data_ptr(), _lib.stream_handle(dev)),
-                       "fetode_driven_fixed_backward_x")
-            tg, tq, _ = ctx.grids
-            gx = driven_series_grad(tq, 0, tg, adj_u, B, ne, 1, B, None, 0, D)
-        else:
-            _lib.check(lib.fetode_driven_fixed_backward(*args, _lib.stream_handle(dev)), "fetode_driven_fixed_backward")
-        want = ctx.needs_input_grad[4:]
-        grads = [None] * 7
-        if any(want) and ne and _DRIVEN_PARAM_GRADS[0]:
-            grads = driven_param_grads(ctx.d, [_lib.f32c(p) for p in params], want, B, ne, 1, B, None, 0, prev0,
-                                       thx, tphi, adj)
-        elif any(want) and ne:
-            grads = _driven_param_sums_generic(f, params[5], want, thx, tphi, adj,
-                                               lambda: torch.cat([prev0.unsqueeze(0), thx[:-1]], dim=0))
-        elif any(want):
-            grads = [torch.zeros_like(p) if w else None for p, w in zip(params, want)]
+        gh0, gx, grads = _driven_fixed_backward("fixed", ctx, _lib.RK4, dtv, prev0, thx, tphi, grad,
+                                                lambda: ctx.grids[:2], params, ctx.needs_input_grad[4:])
         return (None, gx, None, gh0 if ctx.needs_input_grad[3] else None, *grads)
 
 
@@ -924,35 +963,12 @@ def driven_grid_recognise(func, y0, t, tc, step_size, reversed_, method_code):
     """(x (B, T, D), t_grid on y0's GPU) of a solve the grid path reproduces, or None:
     driven_grid_eligible and driven_recognise's tensor rules (a driving series that requires grad needs
     set_driven_series_grad)."""
-    if y0.dim() != 2 or y0.dtype != torch.float32 or not y0.is_cuda:
-        return None
-    if not driven_grid_eligible(func, t, tc, step_size, reversed_, method_code):
-        return None
-    x = _driven_series(func, y0)
-    return None if x is None else (x, _driven_grid(tc, y0.device)[0])
+    rec = _driven_recognise(driven_grid_eligible, func, y0, t, tc, step_size, reversed_, method_code)
+    return None if rec is None else (rec[0], rec[1][0])
 
 
 def _driven_grid_launch(f, plan, d, method_code, h0, u, coef, prev0, n_steps, tape):
-    lib = _lib.load()
-    dev = h0.device
-    B, H = h0.shape
-    In = f.basis.in_dim
-    ne = n_steps * _GRID_STAGES[method_code]
-    sol = torch.empty(n_steps + 1, B, H, device=dev, dtype=torch.float32)
-    sol[0] = h0
-    prev_out = torch.empty(B, In, device=dev, dtype=torch.float32)
-    args = [_lib.ctypes.byref(d), plan.data_ptr(), method_code, h0.data_ptr(), B, u.data_ptr(), u.shape[0], 0,
-            coef.data_ptr(), n_steps, prev0.data_ptr(), sol[1:].data_ptr(), prev_out.data_ptr()]
-    if tape:
-        thx = torch.empty(ne, B, In, device=dev, dtype=torch.float32)
-        tphi = torch.empty(ne, B, H, device=dev, dtype=torch.float32)
-        _lib.check(lib.fetode_driven_grid_tape(*args, thx.data_ptr(), tphi.data_ptr(), _lib.stream_handle(dev)),
-                   "fetode_driven_grid_tape")
-    else:
-        thx = tphi = None
-        _lib.check(lib.fetode_driven_grid(*args, _lib.stream_handle(dev)), "fetode_driven_grid")
-    f.basis._prev = prev_out   # prev_x <- the last evaluation's input (ferro_class.py:409)
-    return sol, thx, tphi
+    return _driven_family_launch("grid", f, plan, d, method_code, h0, u, coef, prev0, n_steps, tape)
 
 
 class _DrivenGridFn(torch.autograd.Function):
@@ -974,36 +990,9 @@ class _DrivenGridFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad):
-        lib = _lib.load()
         tg, tq, coef, prev0, thx, tphi, *params = ctx.saved_tensors
-        f, n_steps = ctx.f, ctx.n_steps
-        dev = grad.device
-        g = _lib.f32c(grad)
-        ne, B, H = tphi.shape
-        In = thx.shape[2]
-        adj = torch.empty_like(tphi)
-        gh0 = torch.empty(B, H, device=dev, dtype=torch.float32)
-        args = [_lib.ctypes.byref(ctx.d), ctx.plan.data_ptr(), ctx.method, B, coef.data_ptr(), n_steps,
-                prev0.data_ptr(), thx.data_ptr(), tphi.data_ptr(), g.data_ptr(), adj.data_ptr(), gh0.data_ptr()]
-        gx = None
-        if ctx.needs_input_grad[1]:
-            D = In - H
-            adj_u = torch.empty(ne, B, D, device=dev, dtype=torch.float32)
-            _lib.check(lib.fetode_driven_grid_backward_x(*args, adj_u.data_ptr(), _lib.stream_handle(dev)),
-                       "fetode_driven_grid_backward_x")
-            gx = driven_series_grad(tq, 0, tg, adj_u, B, ne, 1, B, None, 0, D)
-        else:
-            _lib.check(lib.fetode_driven_grid_backward(*args, _lib.stream_handle(dev)), "fetode_driven_grid_backward")
-        want = ctx.needs_input_grad[8:]
-        grads = [None] * 7
-        if any(want) and ne and _DRIVEN_PARAM_GRADS[0]:
-            grads = driven_param_grads(ctx.d, [_lib.f32c(p) for p in params], want, B, ne, 1, B, None, 0, prev0,
-                                       thx, tphi, adj)
-        elif any(want) and ne:
-            grads = _driven_param_sums_generic(f, params[5], want, thx, tphi, adj,
-                                               lambda: torch.cat([prev0.unsqueeze(0), thx[:-1]], dim=0))
-        elif any(want):
-            grads = [torch.zeros_like(p) if w else None for p, w in zip(params, want)]
+        gh0, gx, grads = _driven_fixed_backward("grid", ctx, ctx.method, coef, prev0, thx, tphi, grad,
+                                                lambda: (tg, tq), params, ctx.needs_input_grad[8:])
         return (None, gx, None, None, None, None, None, gh0 if ctx.needs_input_grad[7] else None, *grads)
 
 
@@ -1058,19 +1047,10 @@ def _driven_dopri5_inputs(func, y0, tc, reversed_, rtol, atol, options, t):
         return None
     if not driven_dopri5_eligible(func, t, tc, reversed_, rtol, atol, options):
         return None
-    x, tg = func._interp.x, func._interp.t
-    B, H = y0.shape
-    if x.dim() == 2:
-        x = x.unsqueeze(0).expand(B, -1, -1)
-    bas = func.basis
-    T, D = tg.numel(), bas.in_dim - bas.out_dim
-    if (x.dim() != 3 or tuple(x.shape) != (B, T, D) or H != bas.out_dim or x.dtype != torch.float32
-            or x.device != y0.device or tg.device != y0.device):
+    x, tg = _driven_tensor_rules(func, y0), func._interp.t
+    if x is None or tg.device != y0.device:
         return None
-    params = _driven_tensors(func)
-    if any(p.device != y0.device or p.dtype != torch.float32 for p in params):
-        return None
-    return x, tg, params
+    return x, tg, _driven_tensors(func)
 
 
 class DrivenDopri5Solve:
@@ -1293,23 +1273,13 @@ class _DrivenDopri5Fn(torch.autograd.Function):
             _lib.check(_lib.load().fetode_driven_dopri5_backward(*args, _lib.stream_handle(dev)),
                        "fetode_driven_dopri5_backward")
         _DrivenDopri5Fn.last_adj = adj   # every evaluation's output adjoint (tests and tooling)
-        want = ctx.needs_input_grad[8:]
-        grads = [None] * 7
-        if any(want) and _DRIVEN_PARAM_GRADS[0]:
-            # the kernel walks sample b's rows below its own nfev (stats[b, 0]) and reads no others
-            ne = min(max(ctx.rec.nfev), tape.max_ev)
-            if ne > 0:
-                grads = driven_param_grads(ctx.d, [_lib.f32c(p) for p in params], want, B, ne, tape.max_ev, 1,
-                                           tape.stats, 3, ctx.prev0, tape.hx, tape.phi, adj)
-            else:
-                grads = [torch.zeros_like(p) if w else None for p, w in zip(params, want)]
-        elif any(want):
-            # rows at or beyond a sample's nfev are zeros in the tape and in adj, so the sums may run over
-            # the rows up to the batch's longest solve
-            ne = max(ctx.rec.nfev)
-            thx, tphi, adj = tape.hx[:, :ne], tape.phi[:, :ne], adj[:, :ne]
-            grads = _driven_param_sums_generic(f, params[5], want, thx, tphi, adj,
-                                               lambda: tape_prev_rows(thx, ctx.prev0))
+        # the fused entry walks sample b's rows below its own nfev (stats[b, 0]) and reads no others; rows at
+        # or beyond a sample's nfev are zeros in the tape and in adj, so the generic sums may run over the
+        # rows up to the batch's longest solve
+        ne = min(max(ctx.rec.nfev), tape.max_ev)
+        grads = _driven_param_sums(f, ctx.d, params, ctx.needs_input_grad[8:], B, ne, (tape.max_ev, 1, tape.stats, 3),
+                                   ctx.prev0, tape.hx, tape.phi, adj, lambda hx: tape_prev_rows(hx, ctx.prev0),
+                                   rows=lambda t: t[:, :ne])
         return (None, gx, None, gh0 if ctx.needs_input_grad[3] else None, None, None, None, None, *grads)
 
 
