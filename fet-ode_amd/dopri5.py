@@ -18,6 +18,7 @@ from __future__ import annotations
 import atexit
 import math
 import os
+from collections import namedtuple
 
 import numpy as np
 import torch
@@ -256,22 +257,15 @@ def _scalar_request(y0, reversed_, rtol, atol, options) -> bool:
             and isinstance(rtol, (int, float)) and isinstance(atol, (int, float)))
 
 
-def _ecg_shape_ok(func, y0) -> bool:
-    """The ECG field the resident kernels are built for: the sigmoid mixer, the state as wide as
-    the basis input (<= 64) and as the head, no noise, at most 3072 trajectories."""
-    import torch.nn as nn
-    basis = func.feat.basis
-    B, D = y0.shape
-    return (isinstance(func.feat.act, nn.Sigmoid) and D == basis.in_dim and D <= 64 and B <= 3072
-            and func.proj.out_features == D and not basis.use_noise)
-
-
-def _raise_status(status: int, timeout_msg: str, restore=None):
+def _raise_status(status: int, timeout_msg: str, restore=None, before=None):
     """torchdiffeq's assertions from a resident solver's status word.  Status 4 (a grid barrier
     timed out: the workgroups were not co-resident) runs ``restore`` first, which puts the
-    hysteresis memory back to its pre-solve value, so the caller can retry on the host loop."""
+    hysteresis memory back to its pre-solve value, so the caller can retry on the host loop;
+    ``before`` then runs ahead of whatever a non-zero status raises."""
     if status == 4 and restore is not None:
         restore()
+    if status != 0 and before is not None:
+        before()
     if status == 1:
         raise AssertionError("non-finite values in state `y`")
     if status == 2:
@@ -380,18 +374,164 @@ def _drop_last_solve():
 atexit.register(_drop_last_solve)
 
 
+# Host glue of the device-resident solves: what the LV, ECG and wide families share is
+# stated once here; each family keeps its own constants and its own order of decisions.
+
+def _opts_array(options):
+    fs = options.get("first_step")
+    return np.array([float(fs) if fs is not None else 0.0, float(options.get("safety", 0.9)),
+                     float(options.get("ifactor", 10.0)), float(options.get("dfactor", 0.2)),
+                     float(options.get("min_step", 0.0)), float(options.get("max_step", math.inf)),
+                     float(options.get("max_num_steps", 2 ** 31 - 1))], dtype=np.float64)
+
+
+def _ctl_ptrs(opts):
+    """The (opts, tableau) ctypes pointers every resident dopri5 entry takes, for an `_opts_array` result."""
+    return (opts.ctypes.data_as(_lib.ctypes.POINTER(_lib.ctypes.c_double)),
+            _TABLEAU.ctypes.data_as(_lib.ctypes.POINTER(_lib.ctypes.c_float)))
+
+
+def _t_device(tp, dev):
+    tkey = (dev, tuple(tp.tolist()))   # tp is the host copy odeint made; uploads once per grid
+    t_dev = _T_DEV.get(tkey)
+    if t_dev is None:
+        if len(_T_DEV) > 64:
+            _T_DEV.clear()
+        t_dev = _T_DEV[tkey] = tp.to(torch.float64).to(dev)
+    return t_dev
+
+
+def _grad_free(y0, params) -> bool:
+    """Nothing in the solve requires grad: what every inference entry asks before it launches."""
+    return not (torch.is_grad_enabled() and (y0.requires_grad or any(p.requires_grad for p in params)))
+
+
+def _workspace(nbytes, dev, query=None):
+    """The fp32 tensor for a *_workspace byte count.  With ``query`` (the query's name) a negative
+    count is FETODE_EUNSUPPORTED; without it the launch that follows is the one to decline."""
+    if nbytes < 0 and query is not None:
+        _lib.check(_lib.FETODE_EUNSUPPORTED, query)
+    return torch.empty(max(1, nbytes // 4), device=dev, dtype=torch.float32)
+
+
+def _launch_buffers(T, B, D, ws_bytes, dev):
+    """What every resident launch writes: sol, its workspace, stats (nfev, attempts, status: all three written)."""
+    sol = torch.empty(T, B, D, device=dev, dtype=torch.float32)
+    return sol, _workspace(ws_bytes, dev), torch.empty(3, device=dev, dtype=torch.int32)
+
+
+_TIMEOUT = "{}: a grid {} timed out (workgroups not co-resident); the solution is invalid"   # (entry, what)
+
+
+def _resident_done(sol, stats, att, entry, sync, restore):
+    """Every inference launch ends so: `last` first, then the status (raised, or queued in `deferred_status`)."""
+    dopri5_solve.last = ResidentSolve(stats, att)
+    _status_check(stats, _TIMEOUT.format(entry, sync), restore)
+    return sol
+
+
+def _sharded_agreement(group, dev, B, ok):
+    """The vote of a trajectory-sharded request (every rank takes the resident path or none: their kernels
+    exchange norms; a rank that skips it hangs its peers): (XRank, B_total, b_off), or None for the host loop."""
+    from . import dist as D
+    grp = None if group == "world" else group
+    agreed = D.resident_agreement(grp, dev, B, bool(ok and D._RESIDENT_SHARDED[0]))
+    if agreed is None:
+        return None
+    xr = D.XRank.get(grp, dev)
+    if not xr.ok:   # agreed over the group: every rank takes the host loop
+        return None
+    return (xr, *agreed)
+
+
+class _Declined(Exception):
+    """A taped entry refused the launch (FETODE_EUNSUPPORTED, nothing written), or the solve outgrew
+    the wide family's tape budget (the pre-solve memory restored): the caller takes the host path."""
+
+
+# A family's constants of the taped solve: its C entry and what its timeout text says timed out; grow: the
+# (evaluations, attempts) an overflowed solve's re-run gets beyond the exact counts, and the least slack of the
+# size remembered for the next call; FETODE_EUNSUPPORTED is _Declined or an error; where the owner keeps that size
+_TapeRule = namedtuple("_TapeRule", "entry sync grow declines attr")
+_LV_TAPE = _TapeRule("fetode_integrate_dopri5_tape", "reduction", (64, 16), False, "_fetode_d5tape")
+_ECG_TAPE = _TapeRule("fetode_ecg_dopri5_tape", "barrier", (12, 2), True, "_fetode_d5tape")
+_WIDE_TAPE = _TapeRule("fetode_wide_dopri5_tape", "barrier", (12, 2), True, "_fetode_wide_d5tape")
+
+
+def _tape_room(owner, attr):
+    """(cap, max_att) of the ECG and wide families' first launch: the owner's last solve or the first guess."""
+    cap, max_att = getattr(owner, attr, (256, 64))
+    return max(1, int(cap)), max(1, int(max_att))
+
+
+def _taped_solve(rule, owner, room, tape_shape, stats, launch, restore, on_fail=None, fits=None):
+    """The taped forward of the three training functions.  room: (cap, max_att) of the first launch;
+    tape_shape(cap): the fp32 tape's shape for cap evaluations; ``launch(cap, max_att, tape, att) -> rc``
+    runs the solve, which writes ``stats``; ``restore()`` puts the hysteresis memory back to its
+    pre-solve value; ``on_fail()`` runs before any status is raised; ``fits(cap, max_att)``: the wide
+    family's budget for a re-run.  Returns (tape, att, nfev, n_att, cap).  One read of stats per launch.
+    A grid timeout (status 4) leaves the pre-solve memory, so the caller may rerun on the host loop;
+    torchdiffeq's own assertions (1-3) keep the last evaluation's, as the reference's prev_x does when
+    they fire (`_raise_status`, as on the inference paths).  A solve longer than the tape or the log is
+    run again from the same memory with room for all of it (deterministic: the same bits), the old tape
+    — GBs at large B and tight rtol — freed before the larger one is allocated.  `dopri5_solve.last`
+    is set once the pass has succeeded."""
+    cap, max_att = room
+    dev = stats.device
+    more_ev, more_att = rule.grow
+    while True:
+        tape = torch.empty(tape_shape(cap), device=dev, dtype=torch.float32)
+        att = torch.empty(max_att, 4, device=dev, dtype=torch.float64)
+        rc = launch(cap, max_att, tape, att)
+        if rule.declines and rc == _lib.FETODE_EUNSUPPORTED:
+            raise _Declined()
+        _lib.check(rc, rule.entry)
+        nfev, n_att, status = stats.tolist()
+        if status:
+            _raise_status(status, _TIMEOUT.format(rule.entry, rule.sync), restore, on_fail)
+        if nfev <= cap and n_att <= max_att:
+            break
+        restore()
+        cap, max_att = nfev + more_ev, n_att + more_att
+        tape = att = None
+        if fits is not None and not fits(cap, max_att):
+            # more than the budget: the memory is the pre-solve one again, and the caller takes the
+            # host path (at once from the next call on)
+            setattr(owner, rule.attr, (cap, max_att))
+            raise _Declined()
+    setattr(owner, rule.attr, (nfev + max(more_ev, nfev // 8), n_att + max(more_att, n_att // 8)))
+    dopri5_solve.last = ResidentSolve(stats, att)
+    return tape, att, nfev, n_att, cap
+
+
+def _checked_sweep(entry, dev, launch):
+    """A reverse sweep with a status word: ``launch(status pointer) -> rc``, then one read of it."""
+    status = torch.empty(1, device=dev, dtype=torch.int32)
+    _lib.check(launch(status.data_ptr()), entry)
+    _raise_status(int(status.item()), f"{entry}: a grid sum timed out (workgroups not co-resident); "
+                                      "the gradients are invalid")
+
+
+def _ecg_request(func, y0, reversed_, rtol, atol, options) -> bool:
+    """The request is the scalar one and `func` the ECG field the resident kernels are built for:
+    No_MLP_KANODEFunc with the sigmoid mixer, the state as wide as the basis input (<= 64) and as the
+    head, no noise, at most 3072 trajectories."""
+    from .ecg import No_MLP_KANODEFunc
+    if not isinstance(func, No_MLP_KANODEFunc) or not _scalar_request(y0, reversed_, rtol, atol, options):
+        return False
+    basis = func.feat.basis
+    B, D = y0.shape
+    return (isinstance(func.feat.act, torch.nn.Sigmoid) and D == basis.in_dim and D <= 64 and B <= 3072
+            and func.proj.out_features == D and not basis.use_noise)
+
+
 def _try_ecg_resident(func, y0, tp, reversed_, rtol, atol, options):
     """The whole solve in one launch when `func` is the ECG field (No_MLP_KANODEFunc with the
     sigmoid mixer), nothing needs gradients, and the options are the scalar ones."""
-    from .ecg import No_MLP_KANODEFunc
-    if not isinstance(func, No_MLP_KANODEFunc) or not _scalar_request(y0, reversed_, rtol, atol, options):
-        return None
-    if not _ecg_shape_ok(func, y0):
+    if not _ecg_request(func, y0, reversed_, rtol, atol, options) or not _grad_free(y0, func.parameters()):
         return None
     basis = func.feat.basis
     B, D = y0.shape
-    if torch.is_grad_enabled() and (y0.requires_grad or any(p.requires_grad for p in func.parameters())):
-        return None
     lib = _lib.load()
     dev = y0.device
     keep = []
@@ -409,16 +549,13 @@ def _try_ecg_resident(func, y0, tp, reversed_, rtol, atol, options):
     yc = _lib.f32c(y0)
     t_dev = _t_device(tp, dev)
     T = t_dev.numel()
-    sol = torch.empty(T, B, D, device=dev, dtype=torch.float32)
-    branch = torch.empty(B, basis.in_dim, basis.num_basis, device=dev, dtype=torch.float32)
-    ws = torch.empty(max(1, lib.fetode_ecg_dopri5_workspace(B) // 4), device=dev, dtype=torch.float32)
-    stats = torch.empty(3, device=dev, dtype=torch.int32)   # the kernel writes all three
+    sol, ws, stats = _launch_buffers(T, B, D, lib.fetode_ecg_dopri5_workspace(B), dev)
     att = torch.empty(_MAX_TRACE, 4, device=dev, dtype=torch.float64)
+    branch = torch.empty(B, basis.in_dim, basis.num_basis, device=dev, dtype=torch.float32)
     opts = _opts_array(options)
     rc = lib.fetode_ecg_dopri5(
         _lib.ctypes.byref(d), wT.data_ptr(), _lib.ptr(bias), D, prev.data_ptr(), yc.data_ptr(), B, t_dev.data_ptr(),
-        T, float(rtol), float(atol), opts.ctypes.data_as(_lib.ctypes.POINTER(_lib.ctypes.c_double)),
-        _TABLEAU.ctypes.data_as(_lib.ctypes.POINTER(_lib.ctypes.c_float)), sol.data_ptr(), prev.data_ptr(),
+        T, float(rtol), float(atol), *_ctl_ptrs(opts), sol.data_ptr(), prev.data_ptr(),
         branch.data_ptr(), ws.data_ptr(), stats.data_ptr(), att.data_ptr(), _MAX_TRACE,
         _lib.stream_handle(dev))
     if rc == _lib.FETODE_EUNSUPPORTED:   # no resident grid for this batch / width: host-driven loop
@@ -426,13 +563,10 @@ def _try_ecg_resident(func, y0, tp, reversed_, rtol, atol, options):
     _lib.check(rc, "fetode_ecg_dopri5")   # prev_x was rewritten in place (read before, written after)
     old_branch = basis.branch_state
     basis.branch_state = branch
-    dopri5_solve.last = ResidentSolve(stats, att)
 
     def back():
         basis.branch_state = old_branch
-    _status_check(stats, "fetode_ecg_dopri5: a grid barrier timed out (workgroups not co-resident); "
-                         "the solution is invalid", _restorer([(prev, prev0), back]))
-    return sol
+    return _resident_done(sol, stats, att, "fetode_ecg_dopri5", "barrier", _restorer([(prev, prev0), back]))
 
 
 def _try_field_resident(func, y0, tp, reversed_, rtol, atol, options):
@@ -446,7 +580,7 @@ def _try_field_resident(func, y0, tp, reversed_, rtol, atol, options):
     group = options.pop("norm_group", None)
     if field is None or not _scalar_request(y0, reversed_, rtol, atol, options):
         return None
-    if torch.is_grad_enabled() and (y0.requires_grad or any(p.requires_grad for p in field.parameters())):
+    if not _grad_free(y0, field.parameters()):
         return None
     lib = _lib.load()
     dev = y0.device
@@ -454,18 +588,11 @@ def _try_field_resident(func, y0, tp, reversed_, rtol, atol, options):
     handle = make_handle(field, B, dev)
     xr = None
     if group is not None:
-        # trajectory-sharded: every rank must take the resident path, or none (their kernels exchange)
-        from . import dist as D
-        grp = None if group == "world" else group
-        ok = (D._RESIDENT_SHARDED[0] and bool(lib.fetode_fused_supported(handle.ref))
-              and 0 < B <= lib.fetode_integrate_dopri5_max_batch(handle.ref, 1))
-        agreed = D.resident_agreement(grp, dev, B, ok)
+        agreed = _sharded_agreement(group, dev, B, lib.fetode_fused_supported(handle.ref)
+                                    and 0 < B <= lib.fetode_integrate_dopri5_max_batch(handle.ref, 1))
         if agreed is None:
             return None
-        B_total, b_off = agreed
-        xr = D.XRank.get(grp, dev)
-        if not xr.ok:   # agreed over the group: every rank takes the host loop
-            return None
+        xr, B_total, b_off = agreed
     elif B > _resident_cap(lib, handle, lib.fetode_integrate_dopri5_max_batch(handle.ref, 0)):
         # no resident solver for this shape / batch: decide BEFORE pack_state, which rebinds the
         # layers' prev_x to the fused state buffer (a declined launch would leave them there and
@@ -477,51 +604,24 @@ def _try_field_resident(func, y0, tp, reversed_, rtol, atol, options):
     yc = _lib.f32c(y0)
     t_dev = _t_device(tp, dev)
     T = t_dev.numel()
-    sol = torch.empty(T, B, y0.shape[1], device=dev, dtype=torch.float32)
-    ws = torch.empty(max(1, lib.fetode_integrate_dopri5_workspace(B) // 4), device=dev, dtype=torch.float32)
-    stats = torch.empty(3, device=dev, dtype=torch.int32)
+    sol, ws, stats = _launch_buffers(T, B, y0.shape[1], lib.fetode_integrate_dopri5_workspace(B), dev)
     att = torch.empty(_MAX_TRACE, 4, device=dev, dtype=torch.float64)
     opts = _opts_array(options)
-    optp = opts.ctypes.data_as(_lib.ctypes.POINTER(_lib.ctypes.c_double))
-    tabp = _TABLEAU.ctypes.data_as(_lib.ctypes.POINTER(_lib.ctypes.c_float))
+    head = (handle.ref, plan.data_ptr(), yc.data_ptr(), B)
+    rest = (t_dev.data_ptr(), T, float(rtol), float(atol), *_ctl_ptrs(opts), sol.data_ptr(), _lib.ptr(state), mask,
+            ws.data_ptr(), stats.data_ptr(), att.data_ptr(), _MAX_TRACE)
     if xr is not None:
         xd = xr.desc(b_off)
-        rc = lib.fetode_integrate_dopri5_xrank(
-            handle.ref, plan.data_ptr(), yc.data_ptr(), B, B_total, t_dev.data_ptr(), T, float(rtol), float(atol),
-            optp, tabp, sol.data_ptr(), _lib.ptr(state), mask, ws.data_ptr(), stats.data_ptr(), att.data_ptr(),
-            _MAX_TRACE, _lib.ctypes.byref(xd), _lib.stream_handle(dev))
+        rc = lib.fetode_integrate_dopri5_xrank(*head, B_total, *rest, _lib.ctypes.byref(xd), _lib.stream_handle(dev))
     else:
-        rc = lib.fetode_integrate_dopri5(
-            handle.ref, plan.data_ptr(), yc.data_ptr(), B, t_dev.data_ptr(), T, float(rtol), float(atol),
-            optp, tabp, sol.data_ptr(), _lib.ptr(state), mask, ws.data_ptr(), stats.data_ptr(), att.data_ptr(),
-            _MAX_TRACE, _lib.stream_handle(dev))
+        rc = lib.fetode_integrate_dopri5(*head, *rest, _lib.stream_handle(dev))
     if rc == _lib.FETODE_EUNSUPPORTED:   # the grid does not fit one resident launch: host-driven loop
         return None
     _lib.check(rc, "fetode_integrate_dopri5")
     if state is not None:
         unpack_state(field, state)
-    dopri5_solve.last = ResidentSolve(stats, att)
-    _status_check(stats, "fetode_integrate_dopri5: a grid reduction timed out (workgroups not co-resident); "
-                         "the solution is invalid", None if state is None else _restorer([(state, state0)]))
-    return sol
-
-
-def _opts_array(options):
-    fs = options.get("first_step")
-    return np.array([float(fs) if fs is not None else 0.0, float(options.get("safety", 0.9)),
-                     float(options.get("ifactor", 10.0)), float(options.get("dfactor", 0.2)),
-                     float(options.get("min_step", 0.0)), float(options.get("max_step", math.inf)),
-                     float(options.get("max_num_steps", 2 ** 31 - 1))], dtype=np.float64)
-
-
-def _t_device(tp, dev):
-    tkey = (dev, tuple(tp.tolist()))   # tp is the host copy odeint made; uploads once per grid
-    t_dev = _T_DEV.get(tkey)
-    if t_dev is None:
-        if len(_T_DEV) > 64:
-            _T_DEV.clear()
-        t_dev = _T_DEV[tkey] = tp.to(torch.float64).to(dev)
-    return t_dev
+    return _resident_done(sol, stats, att, "fetode_integrate_dopri5", "reduction",
+                          None if state is None else _restorer([(state, state0)]))
 
 
 _TAPE_BYTES0 = 1 << 30    # first-call tape budget; later calls size the tape from the last solve
@@ -535,9 +635,10 @@ class _FusedDopri5Fn(torch.autograd.Function):
     (fetode_integrate_dopri5_tape) that also records the layer inputs and the output of every
     evaluation, the attempt log and the initial-step scalars; the tape is sized from the previous
     solve of the field, and a longer solve is re-run from the same hysteresis state with a larger
-    one.  Backward: ONE resident launch (fetode_integrate_dopri5_backward) — reverse-mode through
-    every evaluation of every attempt, the stage sums, the interpolant, the error norm and the
-    step-size control, like autograd through torchdiffeq (which detaches none of them)."""
+    one (`_taped_solve`).  Backward: ONE resident launch (fetode_integrate_dopri5_backward) —
+    reverse-mode through every evaluation of every attempt, the stage sums, the interpolant, the
+    error norm and the step-size control, like autograd through torchdiffeq (which detaches none of
+    them)."""
 
     @staticmethod
     def forward(ctx, field, handle, y0, t_dev, rtol, atol, opts, *params):
@@ -551,41 +652,23 @@ class _FusedDopri5Fn(torch.autograd.Function):
         state, mask = pack_state(field, B, dev)
         state0 = None if state is None else state.clone()
         per_ev = B * (2 * D + H) * 4
-        cap, max_att = getattr(field, "_fetode_d5tape", (max(64, min(1 << 20, _TAPE_BYTES0 // per_ev)), 4096))
+        cap, max_att = getattr(field, _LV_TAPE.attr, (max(64, min(1 << 20, _TAPE_BYTES0 // per_ev)), 4096))
         cap = max(64, min(cap, _TAPE_GUESS_MAX // per_ev))
-        sol = torch.empty(T, B, D, device=dev, dtype=torch.float32)
-        ws = torch.empty(max(1, lib.fetode_integrate_dopri5_workspace(B) // 4), device=dev, dtype=torch.float32)
-        stats = torch.empty(3, device=dev, dtype=torch.int32)
-        init_rec = torch.zeros(5, device=dev, dtype=torch.float64)
-        optp = opts.ctypes.data_as(_lib.ctypes.POINTER(_lib.ctypes.c_double))
-        tabp = _TABLEAU.ctypes.data_as(_lib.ctypes.POINTER(_lib.ctypes.c_float))
-        while True:
-            tape = torch.empty(cap, B, 2 * D + H, device=dev, dtype=torch.float32)   # x, h, k per evaluation
-            att = torch.empty(max_att, 4, device=dev, dtype=torch.float64)
-            _lib.check(lib.fetode_integrate_dopri5_tape(
-                handle.ref, plan.data_ptr(), y0.data_ptr(), B, t_dev.data_ptr(), T, rtol, atol, optp, tabp,
+        sol, ws, stats = _launch_buffers(T, B, D, lib.fetode_integrate_dopri5_workspace(B), dev)
+        init_rec = torch.zeros(5, device=dev, dtype=torch.float64)   # the initial-step scalars
+        ctl = _ctl_ptrs(opts)
+
+        def launch(cap, max_att, tape, att):   # tape: x, h, k per evaluation
+            return lib.fetode_integrate_dopri5_tape(
+                handle.ref, plan.data_ptr(), y0.data_ptr(), B, t_dev.data_ptr(), T, rtol, atol, *ctl,
                 sol.data_ptr(), _lib.ptr(state), mask, ws.data_ptr(), stats.data_ptr(), att.data_ptr(), max_att,
-                tape.data_ptr(), cap, init_rec.data_ptr(), _lib.stream_handle(dev)),
-                "fetode_integrate_dopri5_tape")
-            nfev, n_att, status = stats.tolist()
-            if status == 4 and state is not None:
-                # a grid timeout leaves the pre-solve memory (the caller may rerun on the host loop);
-                # torchdiffeq's own assertions (1-3) keep the last evaluation's, as the reference's
-                # prev_x does when they fire — the same rule as _raise_status on the inference paths
-                state.copy_(state0)
-            if status != 0 and state is not None:
-                unpack_state(field, state)
-            _raise_status(status, "fetode_integrate_dopri5_tape: a grid reduction timed out (workgroups not "
-                                  "co-resident); the solution is invalid")
-            if nfev <= cap and n_att <= max_att:
-                break
-            if state is not None:   # the tape ran out: the same solve again with room for all of it
-                state.copy_(state0)
-            cap, max_att = nfev + 64, n_att + 16
-        field._fetode_d5tape = (nfev + max(64, nfev // 8), n_att + max(16, n_att // 8))
-        if state is not None:
-            unpack_state(field, state)
-        dopri5_solve.last = ResidentSolve(stats, att)
+                tape.data_ptr(), cap, init_rec.data_ptr(), _lib.stream_handle(dev))
+
+        unpack = (lambda: None) if state is None else (lambda: unpack_state(field, state))
+        tape, att, nfev, n_att, _ = _taped_solve(_LV_TAPE, field, (cap, max_att), lambda cap: (cap, B, 2 * D + H),
+                                                 stats, launch, _restorer([] if state is None else [(state, state0)]),
+                                                 on_fail=unpack)
+        unpack()
         ctx.field, ctx.handle, ctx.B, ctx.mask = field, handle, B, mask
         ctx.plan = pin_plan(field, plan)
         ctx.t_dev, ctx.rtol, ctx.atol, ctx.opts = t_dev, rtol, atol, opts
@@ -624,20 +707,13 @@ class _FusedDopri5Fn(torch.autograd.Function):
             kg[l] = _lib.KANLinearGrad(*[_lib.ptr(gbuf(p)) for p in kan_params(kan)])
             if fg is not None:
                 fg[l] = _lib.FerroGrad(*[_lib.ptr(gbuf(getattr(fer, n))) for n in FERRO_PARAM_NAMES])
-        nbytes = lib.fetode_integrate_dopri5_backward_workspace_ev(ctx.handle.ref, B, ctx.n_ev)
-        if nbytes < 0:
-            _lib.check(_lib.FETODE_EUNSUPPORTED, "fetode_integrate_dopri5_backward_workspace_ev")
-        ws = torch.empty(max(1, nbytes // 4), device=dev, dtype=torch.float32)
-        status = torch.empty(1, device=dev, dtype=torch.int32)
-        _lib.check(lib.fetode_integrate_dopri5_backward(
+        ws = _workspace(lib.fetode_integrate_dopri5_backward_workspace_ev(ctx.handle.ref, B, ctx.n_ev), dev,
+                        "fetode_integrate_dopri5_backward_workspace_ev")
+        _checked_sweep("fetode_integrate_dopri5_backward", dev, lambda status: lib.fetode_integrate_dopri5_backward(
             ctx.handle.ref, ctx.plan.data_ptr(), B, ctx.t_dev.data_ptr(), ctx.t_dev.numel(), ctx.rtol, ctx.atol,
-            ctx.opts.ctypes.data_as(_lib.ctypes.POINTER(_lib.ctypes.c_double)),
-            _TABLEAU.ctypes.data_as(_lib.ctypes.POINTER(_lib.ctypes.c_float)), g.data_ptr(), tape.data_ptr(),
-            ctx.n_ev, att.data_ptr(), ctx.n_att, init_rec.data_ptr(),
-            _lib.ptr(state0), ctx.mask, _lib.ptr(gy0), kg, fg, ws.data_ptr(), status.data_ptr(),
-            _lib.stream_handle(dev)), "fetode_integrate_dopri5_backward")
-        _raise_status(int(status.item()), "fetode_integrate_dopri5_backward: a grid sum timed out (workgroups "
-                                          "not co-resident); the gradients are invalid")
+            *_ctl_ptrs(ctx.opts), g.data_ptr(), tape.data_ptr(), ctx.n_ev, att.data_ptr(), ctx.n_att,
+            init_rec.data_ptr(), _lib.ptr(state0), ctx.mask, _lib.ptr(gy0), kg, fg, ws.data_ptr(), status,
+            _lib.stream_handle(dev)))
         pgrads = [grads.get(id(p)) if w else None for p, w in zip(params, want)]
         return (None, None, gy0, None, None, None, None, *pgrads)
 
@@ -676,18 +752,14 @@ def _try_field_resident_train(func, y0, tp, reversed_, rtol, atol, options):
                                 _opts_array(options), *params)
 
 
-class _EcgDeclined(Exception):
-    """fetode_ecg_dopri5_tape refused the launch (FETODE_EUNSUPPORTED, nothing written)."""
-
-
 class _EcgDopri5Fn(torch.autograd.Function):
     """Training through the device-resident dopri5 solve of the ECG field (the reference's own
     training call: odeint(self.odefunc, h0, [0, 1], method="dopri5") then loss.backward(),
     train_ecg_kan_fet_nn_ode.py:551-572, :575-617).  Forward: ONE launch (fetode_ecg_dopri5_tape)
     that also records every evaluation's input and output, the attempt log and the initial-step
     scalars; the tape is sized from the module's previous solve, and a longer solve is re-run from
-    the saved prev_x with a larger one.  Backward: ONE resident launch that walks the attempts
-    backwards (fetode_ecg_dopri5_backward) plus the parameter sums over the stacked evaluations."""
+    the saved prev_x with a larger one (`_taped_solve`).  Backward: ONE resident launch that walks the
+    attempts backwards (fetode_ecg_dopri5_backward) plus the parameter sums over the stacked evaluations."""
 
     @staticmethod
     def forward(ctx, func, y0, t_dev, rtol, atol, opts, w, b, k, Ec, Ps, bias):
@@ -704,38 +776,21 @@ class _EcgDopri5Fn(torch.autograd.Function):
         bc = _lib.f32c(b.detach()) if b is not None else None
         prev = basis._prev_for(dev)
         prev0 = prev.clone()   # the reverse sweep's first memory; restored before a re-run / on a timeout
-        cap, max_att = getattr(func, "_fetode_d5tape", (256, 64))
-        cap, max_att = max(1, int(cap)), max(1, int(max_att))
-        sol = torch.empty(T, B, D, device=dev, dtype=torch.float32)
+        sol, ws, stats = _launch_buffers(T, B, D, lib.fetode_ecg_dopri5_workspace(B), dev)
+        init_rec = torch.zeros(5, device=dev, dtype=torch.float64)   # the initial-step scalars
         branch = torch.empty(B, basis.in_dim, basis.num_basis, device=dev, dtype=torch.float32)
-        ws = torch.empty(max(1, lib.fetode_ecg_dopri5_workspace(B) // 4), device=dev, dtype=torch.float32)
-        stats = torch.empty(3, device=dev, dtype=torch.int32)
-        init_rec = torch.zeros(5, device=dev, dtype=torch.float64)
-        optp = opts.ctypes.data_as(_lib.ctypes.POINTER(_lib.ctypes.c_double))
-        tabp = _TABLEAU.ctypes.data_as(_lib.ctypes.POINTER(_lib.ctypes.c_float))
-        while True:
-            tape = torch.empty(cap, 2, B, D, device=dev, dtype=torch.float32)   # x_e, k_e per evaluation
-            att = torch.empty(max_att, 4, device=dev, dtype=torch.float64)
-            rc = lib.fetode_ecg_dopri5_tape(
+        ctl = _ctl_ptrs(opts)
+
+        def launch(cap, max_att, tape, att):   # tape: x_e, k_e per evaluation
+            return lib.fetode_ecg_dopri5_tape(
                 _lib.ctypes.byref(d), wT.data_ptr(), _lib.ptr(bc), D, prev.data_ptr(), y0.data_ptr(), B,
-                t_dev.data_ptr(), T, rtol, atol, optp, tabp, sol.data_ptr(), prev.data_ptr(), branch.data_ptr(),
+                t_dev.data_ptr(), T, rtol, atol, *ctl, sol.data_ptr(), prev.data_ptr(), branch.data_ptr(),
                 ws.data_ptr(), stats.data_ptr(), att.data_ptr(), max_att, tape.data_ptr(), cap, init_rec.data_ptr(),
                 _lib.stream_handle(dev))
-            if rc == _lib.FETODE_EUNSUPPORTED:
-                raise _EcgDeclined()
-            _lib.check(rc, "fetode_ecg_dopri5_tape")
-            nfev, n_att, status = stats.tolist()
-            if status == 4:
-                prev.copy_(prev0)   # a grid timeout leaves the pre-solve memory (as the inference path)
-            _raise_status(status, "fetode_ecg_dopri5_tape: a grid barrier timed out (workgroups not co-resident); "
-                                  "the solution is invalid")
-            if nfev <= cap and n_att <= max_att:
-                break
-            prev.copy_(prev0)   # the tape ran out: the same solve again with room for all of it
-            cap, max_att = nfev + 12, n_att + 2
-        func._fetode_d5tape = (nfev + max(12, nfev // 8), n_att + max(2, n_att // 8))
+
+        tape, att, nfev, n_att, _ = _taped_solve(_ECG_TAPE, func, _tape_room(func, _ECG_TAPE.attr),
+                                                 lambda cap: (cap, 2, B, D), stats, launch, _restorer([(prev, prev0)]))
         basis.branch_state = branch
-        dopri5_solve.last = ResidentSolve(stats, att)
         ctx.basis, ctx.B, ctx.D = basis, B, D
         ctx.t_dev, ctx.rtol, ctx.atol, ctx.opts = t_dev, rtol, atol, opts
         ctx.n_ev, ctx.n_att, ctx.has_b = nfev, n_att, b is not None
@@ -760,20 +815,13 @@ class _EcgDopri5Fn(torch.autograd.Function):
         gw = buf(6, *wc.shape)
         gbh = buf(7, D) if ctx.has_b else None
         gp = [buf(8 + i, basis.in_dim, basis.num_basis) for i in range(4)]
-        nbytes = lib.fetode_ecg_dopri5_backward_workspace(_lib.ctypes.byref(d), B, ctx.n_ev)
-        if nbytes < 0:
-            _lib.check(_lib.FETODE_EUNSUPPORTED, "fetode_ecg_dopri5_backward_workspace")
-        ws = torch.empty(max(1, nbytes // 4), device=dev, dtype=torch.float32)
-        status = torch.empty(1, device=dev, dtype=torch.int32)
-        _lib.check(lib.fetode_ecg_dopri5_backward(
+        ws = _workspace(lib.fetode_ecg_dopri5_backward_workspace(_lib.ctypes.byref(d), B, ctx.n_ev), dev,
+                        "fetode_ecg_dopri5_backward_workspace")
+        _checked_sweep("fetode_ecg_dopri5_backward", dev, lambda status: lib.fetode_ecg_dopri5_backward(
             _lib.ctypes.byref(d), wc.data_ptr(), D, prev0.data_ptr(), B, ctx.t_dev.data_ptr(), ctx.t_dev.numel(),
-            ctx.rtol, ctx.atol, ctx.opts.ctypes.data_as(_lib.ctypes.POINTER(_lib.ctypes.c_double)),
-            _TABLEAU.ctypes.data_as(_lib.ctypes.POINTER(_lib.ctypes.c_float)), g.data_ptr(), tape.data_ptr(),
+            ctx.rtol, ctx.atol, *_ctl_ptrs(ctx.opts), g.data_ptr(), tape.data_ptr(),
             ctx.n_ev, att.data_ptr(), ctx.n_att, init_rec.data_ptr(), _lib.ptr(gy0), _lib.ptr(gw), _lib.ptr(gbh),
-            *[_lib.ptr(t) for t in gp], ws.data_ptr(), status.data_ptr(), _lib.stream_handle(dev)),
-            "fetode_ecg_dopri5_backward")
-        _raise_status(int(status.item()), "fetode_ecg_dopri5_backward: a grid sum timed out (workgroups not "
-                                          "co-resident); the gradients are invalid")
+            *[_lib.ptr(t) for t in gp], ws.data_ptr(), status, _lib.stream_handle(dev)))
         return (None, gy0, None, None, None, None, gw, gbh, *gp)
 
 
@@ -811,25 +859,86 @@ def _try_ecg_resident_train(func, y0, tp, reversed_, rtol, atol, options):
     """The taped resident solve + reverse sweep when `func` is the ECG field with the sigmoid mixer,
     something needs gradients, the solve is forward in time, the options and tolerances are the
     scalar ones and the batch fits both resident grids; None otherwise (the caller's host path)."""
-    from .ecg import No_MLP_KANODEFunc
-    if not isinstance(func, No_MLP_KANODEFunc) or not _scalar_request(y0, reversed_, rtol, atol, options):
+    if not _ecg_request(func, y0, reversed_, rtol, atol, options):
         return None
     basis = func.feat.basis
-    B, D = y0.shape
-    if not _ecg_shape_ok(func, y0) or B <= 0 or basis.in_dim * basis.num_basis > 768:
+    B = y0.shape[0]
+    if B <= 0 or basis.in_dim * basis.num_basis > 768:
         return None
     lib = _lib.load()
     keep = []
     d = basis.desc(keep)
     if B > lib.fetode_ecg_dopri5_backward_max_batch(_lib.ctypes.byref(d)):
         return None
-    dev = y0.device
     try:
-        return _EcgDopri5Fn.apply(func, y0.to(torch.float32).contiguous(), _t_device(tp, dev), float(rtol),
+        return _EcgDopri5Fn.apply(func, y0.to(torch.float32).contiguous(), _t_device(tp, y0.device), float(rtol),
                                   float(atol), _opts_array(options), func.proj.weight, func.proj.bias, basis.k,
                                   basis.Ec, basis.Ps, basis.bias)
-    except _EcgDeclined:
+    except _Declined:
         return None
+
+
+# ---- wide KAN-FET (fetode_wide_dopri5*)
+def _wide_recognise(func, y0, reversed_, rtol, atol, options):
+    """Stage 1 of the wide recognition, the only checks that may return before a sharded request's
+    vote: `func` is a tagged field with Ferro layers, exactly two of them plain (the constant branch
+    sign, no noise), and the request is the scalar one (``options`` without norm_group).  The field
+    and its layers [(KANLinear, Ferro)] * 2, or None."""
+    from .autograd_ops import field_layers
+    from .odeint import fused_field
+    field = fused_field(func)
+    if field is None or not _scalar_request(y0, reversed_, rtol, atol, options):
+        return None
+    if not getattr(field, "has_ferro", False):
+        return None
+    layers = field_layers(field)
+    if len(layers) != 2 or any(f is None or f._bsign is not None or f.use_noise for _, f in layers):
+        return None
+    return field, layers
+
+
+def _wide_eligible(layers, y0, grads_ok):
+    """Stage 2, the verdict (in a sharded request: this rank's vote, never an early return): a
+    non-empty batch, the D -> H -> D chain with equal num_basis, the caller's gradient rule, and a
+    wide plan for both layers.  The two plan entries, or None."""
+    from .autograd_ops import wide_plan
+    (k0, f0), (k1, f1) = layers
+    B, D = y0.shape
+    H = k0.out_features
+    if (B <= 0 or D != k0.in_features or k1.in_features != H or k1.out_features != D
+            or f0.num_basis != f1.num_basis or not grads_ok):
+        return None
+    e0, e1 = wide_plan(k0, f0, y0.device), wide_plan(k1, f1, y0.device)
+    return None if e0 is None or e1 is None else (e0, e1)
+
+
+def _wide_memory(fs, B, widths, dev):
+    """The two layers' hysteresis memory for a launch: (mask, prev, snap, out), a pair each.  A layer
+    whose memory fails the first-call rule of FerroelectricBasis._needs_reinit (ferro_class.py:373-378:
+    batch, device, dtype) has its mask bit set — the kernel initialises it — and prev = snap = None; a
+    matching but non-contiguous memory is the same state, made contiguous.  snap: a copy of prev (the
+    timeout / re-run restore, the reverse sweep's first memory).  out: where the kernel leaves prev_x
+    (prev itself unless the bit is set); the caller binds it to the layer's _prev after the launch."""
+    mask, prev, snap, out = 0, [], [], []
+    for l, (f, width) in enumerate(zip(fs, widths)):
+        p = f._prev
+        if p.shape != (B, width) or p.device != dev or p.dtype != torch.float32:
+            mask |= 1 << l
+            p = None
+        elif not p.is_contiguous():
+            p = f._prev = p.contiguous()
+        prev.append(p)
+        snap.append(None if p is None else p.clone())
+        out.append(torch.empty(B, width, device=dev, dtype=torch.float32) if p is None else p)
+    return mask, prev, snap, out
+
+
+def _wide_tape_fits(lib, e0, e1, B, per_ev, cap, max_att) -> bool:
+    """The tape of `cap` evaluations plus the sweep's workspace for `max_att` attempts are within
+    set_resident_wide_training's budget (and the sweep has a workspace at all)."""
+    by = _lib.ctypes.byref
+    sweep = lib.fetode_wide_dopri5_backward_workspace(by(e0[1]), by(e0[2]), by(e1[1]), by(e1[2]), B, max_att)
+    return sweep >= 0 and cap * per_ev * 4 + sweep <= _WIDE_RESIDENT_TRAIN[1]
 
 
 class _WideDopri5Fn(torch.autograd.Function):
@@ -838,11 +947,11 @@ class _WideDopri5Fn(torch.autograd.Function):
     loss.backward(), train_kan_fet_ett.py:192, :312-335).  Forward: ONE launch
     (fetode_wide_dopri5_tape) that also records every evaluation's layer inputs and output, the
     attempt log and the initial-step scalars; the tape is sized from the module's previous solve
-    (func._fetode_wide_d5tape), and a longer solve is re-run from the saved memory with room.
-    Backward: fetode_wide_dopri5_backward, a sequence of launches without a read-back that walks the
-    attempts backwards and sums the parameter gradients over stacked (evaluation, row) chunks.
-    flat0 / flat1: each layer's parameters as one tensor (autograd_ops._flat_params), so each layer
-    gets its gradients back as one tensor."""
+    (func._fetode_wide_d5tape), and a longer solve is re-run from the saved memory with room
+    (`_taped_solve`).  Backward: fetode_wide_dopri5_backward, a sequence of launches without a
+    read-back that walks the attempts backwards and sums the parameter gradients over stacked
+    (evaluation, row) chunks.  flat0 / flat1: each layer's parameters as one tensor
+    (autograd_ops._flat_params), so each layer gets its gradients back as one tensor."""
 
     @staticmethod
     def forward(ctx, func, field, y0, t_dev, rtol, atol, opts, ents, layouts, flat0, flat1):
@@ -854,73 +963,25 @@ class _WideDopri5Fn(torch.autograd.Function):
         B, D = y0.shape
         H = k0.out_features
         T = t_dev.numel()
-
-        def mem(f, width):   # the first-call rule of FerroelectricBasis._needs_reinit (as _try_wide_resident)
-            p = f._prev
-            fresh = p.shape != (B, width) or p.device != dev or p.dtype != torch.float32
-            if not fresh and not p.is_contiguous():
-                p = f._prev = p.contiguous()
-            return fresh, p
-
-        re0, p0 = mem(f0, D)
-        re1, p1 = mem(f1, H)
-        # the memory before the solve: the reverse sweep's first memory; restored before a re-run / on a timeout
-        s0 = None if re0 else p0.clone()
-        s1 = None if re1 else p1.clone()
-        st0 = torch.empty(B, D, device=dev, dtype=torch.float32) if re0 else p0   # prev_x after the solve
-        st1 = torch.empty(B, H, device=dev, dtype=torch.float32) if re1 else p1
-        mask = (1 if re0 else 0) | (2 if re1 else 0)
+        mask, prev, (s0, s1), (st0, st1) = _wide_memory((f0, f1), B, (D, H), dev)
         per_ev = B * (2 * D + H)
-        cap, max_att = getattr(func, "_fetode_wide_d5tape", (256, 64))
-        cap, max_att = max(1, int(cap)), max(1, int(max_att))
-        sol = torch.empty(T, B, D, device=dev, dtype=torch.float32)
-        ws = torch.empty(max(1, lib.fetode_wide_dopri5_workspace(B, D, H) // 4), device=dev, dtype=torch.float32)
-        stats = torch.empty(3, device=dev, dtype=torch.int32)
-        init_rec = torch.zeros(5, device=dev, dtype=torch.float64)
+        sol, ws, stats = _launch_buffers(T, B, D, lib.fetode_wide_dopri5_workspace(B, D, H), dev)
+        init_rec = torch.zeros(5, device=dev, dtype=torch.float64)   # the initial-step scalars
         by = _lib.ctypes.byref
-        optp = opts.ctypes.data_as(_lib.ctypes.POINTER(_lib.ctypes.c_double))
-        tabp = _TABLEAU.ctypes.data_as(_lib.ctypes.POINTER(_lib.ctypes.c_float))
+        ctl = _ctl_ptrs(opts)
 
-        def restore():
-            with torch.no_grad():
-                if s0 is not None:
-                    p0.copy_(s0)
-                if s1 is not None:
-                    p1.copy_(s1)
-
-        while True:
-            tape = torch.empty(cap * per_ev, device=dev, dtype=torch.float32)   # planes x | h | k
-            att = torch.empty(max_att, 4, device=dev, dtype=torch.float64)
-            rc = lib.fetode_wide_dopri5_tape(
+        def launch(cap, max_att, tape, att):   # tape: planes x | h | k
+            return lib.fetode_wide_dopri5_tape(
                 by(e0[1]), by(e0[2]), e0[0].data_ptr(), by(e1[1]), by(e1[2]), e1[0].data_ptr(), y0.data_ptr(), B,
-                _lib.ptr(s0), _lib.ptr(s1), mask, t_dev.data_ptr(), T, rtol, atol, optp, tabp, sol.data_ptr(),
+                _lib.ptr(s0), _lib.ptr(s1), mask, t_dev.data_ptr(), T, rtol, atol, *ctl, sol.data_ptr(),
                 st0.data_ptr(), st1.data_ptr(), ws.data_ptr(), stats.data_ptr(), att.data_ptr(), max_att,
                 tape.data_ptr(), cap, init_rec.data_ptr(), _lib.stream_handle(dev))
-            if rc == _lib.FETODE_EUNSUPPORTED:
-                raise _WideDeclined()
-            _lib.check(rc, "fetode_wide_dopri5_tape")
-            nfev, n_att, status = stats.tolist()
-            if status == 4:
-                restore()   # a grid timeout leaves the pre-solve memory (as the inference path)
-            _raise_status(status, "fetode_wide_dopri5_tape: a grid barrier timed out (workgroups not co-resident); "
-                                  "the solution is invalid")
-            if nfev <= cap and n_att <= max_att:
-                break
-            restore()   # the tape ran out: the same solve again with room for all of it
-            cap, max_att = nfev + 12, n_att + 2
-            del tape, att   # freed before the larger ones are allocated
-            sweep = lib.fetode_wide_dopri5_backward_workspace(by(e0[1]), by(e0[2]), by(e1[1]), by(e1[2]), B, max_att)
-            if sweep < 0 or cap * per_ev * 4 + sweep > _WIDE_RESIDENT_TRAIN[1]:
-                # the solve needs more than set_resident_wide_training's budget: the memory is the
-                # pre-solve one again, and the caller takes the host path (at once from the next call on)
-                func._fetode_wide_d5tape = (cap, max_att)
-                raise _WideDeclined()
-        func._fetode_wide_d5tape = (nfev + max(12, nfev // 8), n_att + max(2, n_att // 8))
-        if re0:
-            f0._prev = st0
-        if re1:
-            f1._prev = st1
-        dopri5_solve.last = ResidentSolve(stats, att)
+
+        tape, att, nfev, n_att, cap = _taped_solve(
+            _WIDE_TAPE, func, _tape_room(func, _WIDE_TAPE.attr), lambda cap: (cap * per_ev,), stats, launch,
+            _restorer([(p, s) for p, s in zip(prev, (s0, s1)) if p is not None]),
+            fits=lambda cap, max_att: _wide_tape_fits(lib, e0, e1, B, per_ev, cap, max_att))
+        f0._prev, f1._prev = st0, st1
         ctx.field, ctx.ents, ctx.layouts, ctx.B, ctx.mask, ctx.cap = field, ents, layouts, B, mask, cap
         ctx.t_dev, ctx.rtol, ctx.atol, ctx.opts = t_dev, rtol, atol, opts
         ctx.n_ev, ctx.n_att = nfev, n_att
@@ -959,23 +1020,15 @@ class _WideDopri5Fn(torch.autograd.Function):
             structs += [kg, fg]
         by = _lib.ctypes.byref
         nbytes = lib.fetode_wide_dopri5_backward_workspace(by(e0[1]), by(e0[2]), by(e1[1]), by(e1[2]), B, ctx.n_att)
-        if nbytes < 0:
-            _lib.check(_lib.FETODE_EUNSUPPORTED, "fetode_wide_dopri5_backward_workspace")
-        ws = torch.empty(max(1, nbytes // 4), device=dev, dtype=torch.float32)
+        ws = _workspace(nbytes, dev, "fetode_wide_dopri5_backward_workspace")
         _lib.check(lib.fetode_wide_dopri5_backward(
             by(e0[1]), by(e0[2]), e0[0].data_ptr(), by(e1[1]), by(e1[2]), e1[0].data_ptr(), B, _lib.ptr(s0),
             _lib.ptr(s1), ctx.mask, ctx.t_dev.data_ptr(), ctx.t_dev.numel(), ctx.rtol, ctx.atol,
-            ctx.opts.ctypes.data_as(_lib.ctypes.POINTER(_lib.ctypes.c_double)),
-            _TABLEAU.ctypes.data_as(_lib.ctypes.POINTER(_lib.ctypes.c_float)), g.data_ptr(), tape.data_ptr(), ctx.cap,
+            *_ctl_ptrs(ctx.opts), g.data_ptr(), tape.data_ptr(), ctx.cap,
             ctx.n_ev, att.data_ptr(), ctx.n_att, init_rec.data_ptr(), _lib.ptr(gy0),
             *[None if s is None else by(s) for s in structs], ws.data_ptr(), _lib.stream_handle(dev)),
             "fetode_wide_dopri5_backward")
         return (None, None, gy0, None, None, None, None, None, None, gflat[0], gflat[1])
-
-
-class _WideDeclined(Exception):
-    """fetode_wide_dopri5_tape refused the launch (FETODE_EUNSUPPORTED, nothing written), or the solve
-    outgrew the tape budget (the pre-solve memory restored)."""
 
 
 _WIDE_RESIDENT_TRAIN = [os.environ.get("FETODE_WIDE_DOPRI5_TAPE", "0") == "1", 16 << 30]
@@ -998,47 +1051,33 @@ def set_resident_wide_training(enabled: bool, tape_bytes=None) -> bool:
 
 def _try_wide_resident_train(func, y0, tp, reversed_, rtol, atol, options):
     """The taped resident solve + reverse sweep when `func` is a tagged two-layer wide KAN-FET field
-    (the shape tests of _try_wide_resident), every parameter of it requires gradients, the solve is
-    single-device (no norm_group), forward in time with scalar tolerances and options, no noise and
-    the constant branch sign, and the tape fits the budget of set_resident_wide_training; None
-    otherwise (the caller's host path).  (odeint detaches t before any solver sees it: no path
-    differentiates the output times.)  _WIDE_RESIDENT_GAP does
-    not apply: it is the inference crossover against the host loop without autograd."""
-    from .autograd_ops import FERRO_PARAM_NAMES, _flat_params, field_layers, kan_params, wide_plan
-    from .odeint import fused_field
-    field = fused_field(func)
-    if field is None or not _scalar_request(y0, reversed_, rtol, atol, options):   # norm_group is no scalar option
+    (`_wide_recognise`, `_wide_eligible`), every parameter of it requires gradients, the solve is
+    single-device (norm_group is no scalar option), forward in time with scalar tolerances and
+    options, no noise and the constant branch sign, and the tape fits the budget of
+    set_resident_wide_training; None otherwise (the caller's host path).  (odeint detaches t before
+    any solver sees it: no path differentiates the output times.)  _WIDE_RESIDENT_GAP does not
+    apply: it is the inference crossover against the host loop without autograd."""
+    from .autograd_ops import FERRO_PARAM_NAMES, _flat_params, kan_params
+    seen = _wide_recognise(func, y0, reversed_, rtol, atol, options)
+    if seen is None:
         return None
-    if not getattr(field, "has_ferro", False):
-        return None
-    layers = field_layers(field)
-    if len(layers) != 2 or any(f is None or f._bsign is not None or f.use_noise for _, f in layers):
+    field, layers = seen
+    ps = [[p for p in kan_params(k) if p is not None] + [getattr(f, n) for n in FERRO_PARAM_NAMES] for k, f in layers]
+    ents = _wide_eligible(layers, y0, all(p.requires_grad for l in ps for p in l))
+    if ents is None:
         return None
     (k0, f0), (k1, f1) = layers
     B, D = y0.shape
     H = k0.out_features
-    dev = y0.device
-    if B <= 0 or D != k0.in_features or k1.in_features != H or k1.out_features != D or f0.num_basis != f1.num_basis:
-        return None
-    ps = [[p for p in kan_params(k) if p is not None] + [getattr(f, n) for n in FERRO_PARAM_NAMES] for k, f in layers]
-    if not all(p.requires_grad for l in ps for p in l):
-        return None
-    e0, e1 = wide_plan(k0, f0, dev), wide_plan(k1, f1, dev)
-    if e0 is None or e1 is None:
-        return None
     lib = _lib.load()
-    by = _lib.ctypes.byref
-    cap, n_att = getattr(func, "_fetode_wide_d5tape", (256, 64))
-    sweep = lib.fetode_wide_dopri5_backward_workspace(by(e0[1]), by(e0[2]), by(e1[1]), by(e1[2]), B, max(1, int(n_att)))
-    if sweep < 0 or lib.fetode_wide_dopri5_workspace(B, D, H) < 0:
-        return None
-    if max(1, int(cap)) * B * (2 * D + H) * 4 + sweep > _WIDE_RESIDENT_TRAIN[1]:
+    room = _tape_room(func, _WIDE_TAPE.attr)
+    if lib.fetode_wide_dopri5_workspace(B, D, H) < 0 or not _wide_tape_fits(lib, *ents, B, B * (2 * D + H), *room):
         return None
     (flat0, lay0), (flat1, lay1) = _flat_params(k0, f0, ps[0]), _flat_params(k1, f1, ps[1])
     try:
-        return _WideDopri5Fn.apply(func, field, y0.to(torch.float32).contiguous(), _t_device(tp, dev), float(rtol),
-                                   float(atol), _opts_array(options), (e0, e1), (lay0, lay1), flat0, flat1)
-    except _WideDeclined:
+        return _WideDopri5Fn.apply(func, field, y0.to(torch.float32).contiguous(), _t_device(tp, y0.device),
+                                   float(rtol), float(atol), _opts_array(options), ents, (lay0, lay1), flat0, flat1)
+    except _Declined:
         return None
 
 
@@ -1049,52 +1088,31 @@ def _try_wide_resident(func, y0, tp, reversed_, rtol, atol, options):
     Trajectory-sharded (options["norm_group"], dist.odeint_sharded): one launch per rank whose
     norms are exchanged between the ranks' kernels (fetode_wide_dopri5_xrank) — every rank takes the
     resident path or none."""
-    from .autograd_ops import field_layers, wide_plan
-    from .odeint import fused_field
-    field = fused_field(func)
     options = dict(options)
     group = options.pop("norm_group", None)
-    if field is None or not _scalar_request(y0, reversed_, rtol, atol, options):
+    seen = _wide_recognise(func, y0, reversed_, rtol, atol, options)
+    if seen is None:
         return None
-    if not getattr(field, "has_ferro", False):
-        return None
-    layers = field_layers(field)
-    if len(layers) != 2 or any(f is None or f._bsign is not None or f.use_noise for _, f in layers):
-        return None
+    field, layers = seen
     (k0, f0), (k1, f1) = layers
     B, D = y0.shape
     H = k0.out_features
     dev = y0.device
-    ok = True
     if group is None and _WIDE_RESIDENT_GAP[0] < B < _WIDE_RESIDENT_GAP[1]:
         # measured crossover (DESIGN.md §4.8): between these batches the per-layer launches beat the
         # persistent grid's tiles plus its three grid barriers per evaluation
         return None
-    if D != k0.in_features or k1.in_features != H or k1.out_features != D or f0.num_basis != f1.num_basis:
-        ok = False
-    if B <= 0:   # an empty shard votes no: every rank then falls back to the host loop together
-        ok = False
-    if torch.is_grad_enabled() and (y0.requires_grad or any(p.requires_grad for p in field.parameters())):
-        ok = False
-    e0 = e1 = None
-    if ok:
-        e0, e1 = wide_plan(k0, f0, dev), wide_plan(k1, f1, dev)
-        ok = e0 is not None and e1 is not None
+    # from here on a sharded rank votes (an empty shard too), never returns: the ranks fall back together
+    ents = _wide_eligible(layers, y0, _grad_free(y0, field.parameters()))
     lib = _lib.load()
     xr = None
     if group is not None:
-        # trajectory-sharded: all ranks take the resident path or none (their kernels exchange norms)
-        from . import dist as Dd
-        grp = None if group == "world" else group
-        agreed = Dd.resident_agreement(grp, dev, B, ok and Dd._RESIDENT_SHARDED[0])
+        agreed = _sharded_agreement(group, dev, B, ents is not None)
         if agreed is None:
             return None
-        B_total, b_off = agreed
-        xr = Dd.XRank.get(grp, dev)
-        if not xr.ok:   # agreed over the group: every rank takes the host loop
-            return None
+        xr, B_total, b_off = agreed
         ws_bytes = lib.fetode_wide_dopri5_xrank_workspace(B, B_total, b_off, D, H)
-    elif not ok:
+    elif ents is None:
         return None
     else:
         ws_bytes = lib.fetode_wide_dopri5_workspace(B, D, H)
@@ -1102,46 +1120,24 @@ def _try_wide_resident(func, y0, tp, reversed_, rtol, atol, options):
         if xr is not None:
             raise RuntimeError("sharded wide dopri5: no workspace for this shard after every rank agreed")
         return None
+    e0, e1 = ents
     yc = _lib.f32c(y0)
-
-    def mem(f, width):
-        # the first-call rule of FerroelectricBasis._needs_reinit (ferro_class.py:373-378): batch,
-        # device, dtype; a matching but non-contiguous memory is the same state, made contiguous
-        p = f._prev
-        fresh = p.shape != (B, width) or p.device != dev or p.dtype != torch.float32
-        if not fresh and not p.is_contiguous():
-            p = f._prev = p.contiguous()
-        return fresh, p
-
-    re0, p0 = mem(f0, D)
-    re1, p1 = mem(f1, H)
-    snap = [(p, p.clone()) for re, p in ((re0, p0), (re1, p1)) if not re]   # for the timeout path
-    st0 = torch.empty(B, D, device=dev, dtype=torch.float32) if re0 else p0   # prev_x after the solve
-    st1 = torch.empty(B, H, device=dev, dtype=torch.float32) if re1 else p1
+    mask, (p0, p1), snap, (st0, st1) = _wide_memory((f0, f1), B, (D, H), dev)
     t_dev = _t_device(tp, dev)
     T = t_dev.numel()
-    sol = torch.empty(T, B, D, device=dev, dtype=torch.float32)
-    ws = torch.empty(max(1, ws_bytes // 4), device=dev, dtype=torch.float32)
-    stats = torch.empty(3, device=dev, dtype=torch.int32)
+    sol, ws, stats = _launch_buffers(T, B, D, ws_bytes, dev)
     att = torch.empty(_MAX_TRACE, 4, device=dev, dtype=torch.float64)
     opts = _opts_array(options)
     by = _lib.ctypes.byref
-    optp = opts.ctypes.data_as(_lib.ctypes.POINTER(_lib.ctypes.c_double))
-    tabp = _TABLEAU.ctypes.data_as(_lib.ctypes.POINTER(_lib.ctypes.c_float))
-    mask = (1 if re0 else 0) | (2 if re1 else 0)
+    head = (by(e0[1]), by(e0[2]), e0[0].data_ptr(), by(e1[1]), by(e1[2]), e1[0].data_ptr(), yc.data_ptr(), B)
+    rest = (_lib.ptr(p0), _lib.ptr(p1), mask, t_dev.data_ptr(), T, float(rtol),
+            float(atol), *_ctl_ptrs(opts), sol.data_ptr(), st0.data_ptr(), st1.data_ptr(), ws.data_ptr(),
+            stats.data_ptr(), att.data_ptr(), _MAX_TRACE)
     if xr is not None:
         xd = xr.desc(b_off)
-        rc = lib.fetode_wide_dopri5_xrank(
-            by(e0[1]), by(e0[2]), e0[0].data_ptr(), by(e1[1]), by(e1[2]), e1[0].data_ptr(), yc.data_ptr(), B, B_total,
-            None if re0 else p0.data_ptr(), None if re1 else p1.data_ptr(), mask, t_dev.data_ptr(), T, float(rtol),
-            float(atol), optp, tabp, sol.data_ptr(), st0.data_ptr(), st1.data_ptr(), ws.data_ptr(), stats.data_ptr(),
-            att.data_ptr(), _MAX_TRACE, by(xd), _lib.stream_handle(dev))
+        rc = lib.fetode_wide_dopri5_xrank(*head, B_total, *rest, by(xd), _lib.stream_handle(dev))
     else:
-        rc = lib.fetode_wide_dopri5(
-            by(e0[1]), by(e0[2]), e0[0].data_ptr(), by(e1[1]), by(e1[2]), e1[0].data_ptr(), yc.data_ptr(), B,
-            None if re0 else p0.data_ptr(), None if re1 else p1.data_ptr(), mask, t_dev.data_ptr(), T, float(rtol),
-            float(atol), optp, tabp, sol.data_ptr(), st0.data_ptr(), st1.data_ptr(), ws.data_ptr(), stats.data_ptr(),
-            att.data_ptr(), _MAX_TRACE, _lib.stream_handle(dev))
+        rc = lib.fetode_wide_dopri5(*head, *rest, _lib.stream_handle(dev))
     if rc == _lib.FETODE_EUNSUPPORTED:
         if xr is not None:   # the peers' kernels are waiting for this rank's norms
             raise RuntimeError("sharded wide dopri5: this rank's launch was refused after every rank agreed: "
@@ -1152,14 +1148,9 @@ def _try_wide_resident(func, y0, tp, reversed_, rtol, atol, options):
 
     def back():
         f0._prev, f1._prev = old
-    if re0:
-        f0._prev = st0
-    if re1:
-        f1._prev = st1
-    dopri5_solve.last = ResidentSolve(stats, att)
-    _status_check(stats, "fetode_wide_dopri5: a grid barrier timed out (workgroups not co-resident); "
-                         "the solution is invalid", _restorer(snap + [back]))
-    return sol
+    f0._prev, f1._prev = st0, st1
+    return _resident_done(sol, stats, att, "fetode_wide_dopri5", "barrier",
+                          _restorer([(p, s) for p, s in zip((p0, p1), snap) if p is not None] + [back]))
 
 
 _RESIDENT = True
@@ -1511,6 +1502,26 @@ def _needs_grad(func, y0) -> bool:
     return True   # a plain callable may close over trainable tensors
 
 
+# The resident solvers in the order tried: (its switch, the try-function by name, looked up at each call so
+# that rebinding one takes effect; it returns the solution or None).  set_resident_dopri5(False) turns all off.
+_INFERENCE = ((lambda: True, "_try_ecg_resident"),
+              (lambda: True, "_try_field_resident"),
+              (lambda: _WIDE_RESIDENT, "_try_wide_resident"))
+_TRAINING = ((lambda: _ECG_RESIDENT_TRAIN, "_try_ecg_resident_train"),
+             (lambda: _WIDE_RESIDENT_TRAIN[0], "_try_wide_resident_train"),
+             (lambda: _RESIDENT_TRAIN, "_try_field_resident_train"))
+
+
+def _first_resident(table, request):
+    if _RESIDENT:
+        for enabled, attempt in table:
+            if enabled():
+                sol = globals()[attempt](*request)
+                if sol is not None:
+                    return sol
+    return None
+
+
 def dopri5_solve(func, y0, tc, tp, reversed_, rtol, atol, options):
     if getattr(func, "_fetode_driven", False):
         # an input-driven field (ecg.InputDrivenKANODEFunc) solved for one row: the one-launch solve with
@@ -1520,27 +1531,14 @@ def dopri5_solve(func, y0, tc, tp, reversed_, rtol, atol, options):
         sol = driven_dopri5_odeint(func, y0, tc, reversed_, rtol, atol, options)
         if sol is not None:
             return sol
-    if _RESIDENT:
-        sol = _try_ecg_resident(func, y0, tp, reversed_, rtol, atol, options)
-        if sol is None:
-            sol = _try_field_resident(func, y0, tp, reversed_, rtol, atol, options)
-        if sol is None and _WIDE_RESIDENT:
-            sol = _try_wide_resident(func, y0, tp, reversed_, rtol, atol, options)
+    request = (func, y0, tp, reversed_, rtol, atol, options)
+    sol = _first_resident(_INFERENCE, request)
+    if sol is not None:
+        return sol
+    if _needs_grad(func, y0):
+        sol = _first_resident(_TRAINING, request)
         if sol is not None:
             return sol
-    if _needs_grad(func, y0):
-        if _RESIDENT and _ECG_RESIDENT_TRAIN:
-            sol = _try_ecg_resident_train(func, y0, tp, reversed_, rtol, atol, options)
-            if sol is not None:
-                return sol
-        if _RESIDENT and _WIDE_RESIDENT_TRAIN[0]:
-            sol = _try_wide_resident_train(func, y0, tp, reversed_, rtol, atol, options)
-            if sol is not None:
-                return sol
-        if _RESIDENT and _RESIDENT_TRAIN:
-            sol = _try_field_resident_train(func, y0, tp, reversed_, rtol, atol, options)
-            if sol is not None:
-                return sol
         solver = _Dopri5Grad(func, y0, rtol, atol, options, reversed_)
         sol = solver.integrate(tp)
         dopri5_solve.last = solver

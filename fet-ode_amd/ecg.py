@@ -1094,7 +1094,7 @@ def driven_dopri5_solve(func, y0, tc, reversed_, rtol, atol, options, reset=Fals
     every row's last evaluation input.  reset: the rows start from the reset hysteresis state (zeros)
     instead of the stored one.  evlog: a (B, max_ev, 1 + D) fp32 tensor that receives every
     evaluation's time and x(t) (tests).  The caller checks the record's status."""
-    from .dopri5 import _TABLEAU, _opts_array
+    from .dopri5 import _ctl_ptrs, _opts_array
     rec = _driven_dopri5_inputs(func, y0, tc, reversed_, rtol, atol, options, t)
     if rec is None:
         return None
@@ -1119,8 +1119,7 @@ def driven_dopri5_solve(func, y0, tc, reversed_, rtol, atol, options, reset=Fals
     opts = _opts_array(options)
     rc = _lib.load().fetode_driven_dopri5(
         _lib.ctypes.byref(d), plan.data_ptr(), h0.data_ptr(), B, xc.data_ptr(), tgc.data_ptr(), T, float(rtol),
-        float(atol), opts.ctypes.data_as(_lib.ctypes.POINTER(_lib.ctypes.c_double)),
-        _TABLEAU.ctypes.data_as(_lib.ctypes.POINTER(_lib.ctypes.c_float)), _lib.ptr(prev0), sol.data_ptr(),
+        float(atol), *_ctl_ptrs(opts), _lib.ptr(prev0), sol.data_ptr(),
         prev_out.data_ptr(), stats.data_ptr(), att.data_ptr(), _DRIVEN_MAX_TRACE, _lib.ptr(evlog),
         0 if evlog is None else evlog.shape[1], _lib.stream_handle(dev))
     if rc == _lib.FETODE_EUNSUPPORTED:   # declined before the launch: nothing was touched
@@ -1163,7 +1162,7 @@ def tape_prev_rows(thx, prev0):
 
 
 def _driven_dopri5_tape_launch(d, plan, h0, xc, tgc, rtol, atol, opts, prev0, max_att):
-    from .dopri5 import _TABLEAU
+    from .dopri5 import _ctl_ptrs
     dev = h0.device
     B, H = h0.shape
     T, D = xc.shape[1], xc.shape[2]
@@ -1178,8 +1177,7 @@ def _driven_dopri5_tape_launch(d, plan, h0, xc, tgc, rtol, atol, opts, prev0, ma
                            init=torch.empty(B, 5, device=dev, dtype=torch.float64), max_ev=max_ev, max_att=max_att)
     rc = _lib.load().fetode_driven_dopri5_tape(
         _lib.ctypes.byref(d), plan.data_ptr(), h0.data_ptr(), B, xc.data_ptr(), tgc.data_ptr(), T, float(rtol),
-        float(atol), opts.ctypes.data_as(_lib.ctypes.POINTER(_lib.ctypes.c_double)),
-        _TABLEAU.ctypes.data_as(_lib.ctypes.POINTER(_lib.ctypes.c_float)), _lib.ptr(prev0), sol.data_ptr(),
+        float(atol), *_ctl_ptrs(opts), _lib.ptr(prev0), sol.data_ptr(),
         prev_out.data_ptr(), stats.data_ptr(), att.data_ptr(), max_att, tape.hx.data_ptr(), tape.phi.data_ptr(),
         tape.t.data_ptr(), tape.slope.data_ptr(), tape.init.data_ptr(), max_ev, _lib.stream_handle(dev))
     if rc == _lib.FETODE_EUNSUPPORTED:   # declined before the launch: nothing was touched
@@ -1247,7 +1245,7 @@ class _DrivenDopri5Fn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad):
-        from .dopri5 import _TABLEAU
+        from .dopri5 import _ctl_ptrs
         params = ctx.saved_tensors
         f, tape, dev = ctx.f, ctx.tape, grad.device
         g = _lib.f32c(grad)
@@ -1255,8 +1253,7 @@ class _DrivenDopri5Fn(torch.autograd.Function):
         adj = torch.empty_like(tape.phi)
         gh0 = torch.empty(B, H, device=dev, dtype=torch.float32)
         args = [_lib.ctypes.byref(ctx.d), ctx.plan.data_ptr(), B, ctx.tg.data_ptr(), T, ctx.tols[0], ctx.tols[1],
-                tape.opts.ctypes.data_as(_lib.ctypes.POINTER(_lib.ctypes.c_double)),
-                _TABLEAU.ctypes.data_as(_lib.ctypes.POINTER(_lib.ctypes.c_float)), _lib.ptr(ctx.prev0),
+                *_ctl_ptrs(tape.opts), _lib.ptr(ctx.prev0),
                 tape.stats.data_ptr(), tape.att.data_ptr(), tape.max_att, tape.hx.data_ptr(), tape.phi.data_ptr(),
                 tape.slope.data_ptr(), tape.init.data_ptr(), tape.max_ev, g.data_ptr(), int(ctx.step_grad),
                 adj.data_ptr(), gh0.data_ptr()]
